@@ -1,7 +1,14 @@
 #!/usr/bin/env python
 """Benchmark of the sq.gr hot path on MI355X (contract: see the task statement / DESIGN.md §Measurement).
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong --total-perms P]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong --total-perms P] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps of the headline and prints its line (the headline's ``roofline`` / ``kernels``
+come from the HIP-event timers of those same steps).  Every other measurement below — ``secondary``, ``legs``,
+``numpy_stream_mode``, ``cpu_baseline``, ``emulated_ranks`` and the detail file — runs only with ``--full`` (the ``--no-*``
+options then leave single parts out).  ``--dump-outputs DIR`` writes what the last timed step returned (rank 0):
+``moments_s1.npy`` / ``moments_s2.npy`` (the step's sums of d and d^2, d = count - expected, float64, exact), ``zscore.npy``
+(the z-scores of that step's permutations alone) and ``counts.npy`` (the observed counts); the inputs depend only on the arguments.
 
 Workload (N=1): ``nhood_enrichment`` permutation test on the 1e6-spot hex grid x 30 clusters that BASELINE.json's
 metric is quoted on (config 5's shape); one *step* = one pass of the hot path over one batch of permutations with
@@ -1302,12 +1309,23 @@ def main() -> None:
     ap.add_argument("--emulate-ranks", type=int, default=8,
                     help="projection for a node this box does not have: run the N rank shards of BASELINE config 5 (--total-perms permutations, strong "
                     "scaling) one after the other on this GPU and print per-shard times; no collective runs, labelled as a projection")
-    ap.add_argument("--detail-out", type=str, default=os.path.join("gpurun_out", "bench_detail.json"),
-                    help="where the full record goes (the final stdout line is the compact one: < 4 KB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: secondary leg, config-3/4 legs, nhood variants, numpy-stream leg, CPU baselines, "
+                    "emulated ranks, and write the detail file (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--detail-out", type=str, default=None,
+                    help="where the full record goes (the final stdout line is the compact one: < 4 KB); default with --full: "
+                    + os.path.join("bench_out", "bench_detail.json"))
     ap.add_argument("--tune", type=str, default="", help="perms_per_pass,blocks_per_batch,batches_per_launch")
     ap.add_argument("--share-devices", action="store_true",
                     help="allow more ranks than GPUs (rank r on device r mod #GPUs, integer all-reduce through the host side channel): tests on a 1-GPU box")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline only
+        args.no_cpu_baseline = args.no_secondary = args.no_legs = args.no_numpy_leg = True
+        args.emulate_ranks = 0
+    elif args.detail_out is None:
+        args.detail_out = os.path.join("bench_out", "bench_detail.json")
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
@@ -1400,6 +1418,11 @@ def main() -> None:
     elapsed = reduce_max(time.perf_counter() - t0)
     kernels = ctx.timer_report()
     ctx.timer_enable(False)
+    if args.dump_outputs and rank == 0 and args.steps > 0:  # what the last timed step handed back, and the z-scores of its permutations
+        dump = {"moments_s1": s1, "moments_s2": s2, "zscore": zscore_from_moments(count, shift, s1, s2, P if strong else P * world), "counts": count}
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(arr, dtype=np.float64))
     rank_devices = [local_rank % max(_lib.device_count(), 1)] if world == 1 else [int(d) for d in _dist.allgather_object(local_rank % max(_lib.device_count(), 1))]
     collective = "none" if world == 1 else ("rccl-in-library (device all-reduce of the moments)" if comm is not None else _dist.collective_kind() + " (host fall-back)")
 
@@ -1710,10 +1733,11 @@ def main() -> None:
         out["pmc_profile"] = counters.get("_status")
         detail_path = None
         try:  # the full record (notes, issue limits, PMC inputs, per-kernel tables): a side file, never the driver's line
-            os.makedirs(os.path.dirname(os.path.abspath(args.detail_out)), exist_ok=True)
-            with open(args.detail_out, "w") as fh:
-                json.dump(out, fh, indent=1)
-            detail_path = args.detail_out
+            if args.detail_out:
+                os.makedirs(os.path.dirname(os.path.abspath(args.detail_out)), exist_ok=True)
+                with open(args.detail_out, "w") as fh:
+                    json.dump(out, fh, indent=1)
+                detail_path = args.detail_out
         except OSError as exc:  # pragma: no cover  (read-only checkout)
             print(f"bench.py: could not write {args.detail_out}: {exc}", file=sys.stderr)
         print(json.dumps(compact_line(out, detail_path)), flush=True)

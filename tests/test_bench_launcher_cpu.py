@@ -61,21 +61,23 @@ def test_ranks_that_hang_are_stopped_at_the_deadline(tmp_path):
 
 
 def test_the_ranks_rendezvous_through_the_socket_group(tmp_path):
-    """The environment the launcher exports is what squidpy_amd._dist's rendezvous reads: 3 ranks meet and sum an array (no GPU)."""
+    """The environment the launcher exports is what squidpy_amd._dist's rendezvous reads: 3 ranks meet and sum an array (no GPU:
+    the host collective is asked for, so that a GPU on the test machine does not put the sum on RCCL, whose banner goes to stdout)."""
     rc, out, err = _run_launcher(f"""
-        import sys
+        import os, sys
         sys.path.insert(0, {ROOT!r})
+        os.environ["SQGR_DIST_COLLECTIVE"] = "host"
         import numpy as np
         from squidpy_amd import _dist
         _dist.init()
         r, w = _dist.world()
         (tot,) = _dist.allreduce_sum_([np.array([r + 1, 10 * (r + 1)], dtype=np.int64)])
         _dist.barrier()
-        print(w, tot.tolist())
+        print(w, tot.tolist(), _dist.collective_kind())
         _dist.shutdown()
         """, 3, tmp_path)
     assert rc == 0, err
-    assert out == ["3 [6, 60]"]
+    assert out == ["3 [6, 60] socket-hub"]
 
 
 def _bench(*argv, env=None):

@@ -1,5 +1,5 @@
 """CPU tests of the ligrec row: the oracle against the golden vectors of the reference's own
-source, against the literal source where /root/reference exists, and the host logic of ``PermutationTest`` (the
+source, against the literal source's outputs on fresh inputs (tests/golden/literal_source_cases.npz), and the host logic of ``PermutationTest`` (the
 reference's validation behaviour, tests/graph/test_ligrec.py:26-152, 436-444).  No device compute here."""
 
 from __future__ import annotations
@@ -17,6 +17,7 @@ from squidpy_amd import AnnDataLite
 from squidpy_amd.gr import PermutationTest, ligrec
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ligrec_reference.npz")
+LITERAL = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "literal_source_cases.npz")
 
 
 @pytest.fixture(scope="module")
@@ -40,20 +41,31 @@ def test_golden_case_c_is_the_reference_nan_layout(gold):
     assert np.isnan(p).sum() == 11 and p[1, 1] == 0.0
 
 
-@pytest.mark.skipif(not ref_shim.available(), reason="needs /root/reference (build container)")
-def test_oracle_matches_literal_reference_source():
+@pytest.fixture(scope="module")
+def literal():
+    """Outputs of the reference's literal source on fresh inputs (tests/golden/make_literal_source_golden.py)."""
+    return np.load(LITERAL)
+
+
+def test_oracle_matches_literal_reference_source(literal):
     rng = np.random.default_rng(3)
     n, g, k = 180, 10, 5
     data = (rng.random((n, g)) < 0.4) * rng.gamma(2.0, 1.0, (n, g))
     cl = rng.integers(0, k, n).astype(np.int32)
     inter = np.array([(i, j) for i in range(g) for j in range(g)], dtype=np.int32)[::4]
     cp = np.array([(a, b) for a in range(k) for b in range(k)], dtype=np.int32)[::2]
-    df = pd.DataFrame(data, columns=list(range(g)))
-    df["clusters"] = pd.Categorical(cl)
-    ref = ref_shim.ligrec()["_analysis"](df, inter, cp, threshold=0.4, n_perms=40, seed=9, n_jobs=1, show_progress_bar=False)
+    for name, arr in (("data", data), ("clusters", cl), ("interactions", inter), ("cpairs", cp)):
+        np.testing.assert_array_equal(arr, literal[f"ligrec_fresh_{name}"], err_msg=name)
+    ref_means, ref_pvalues = literal["ligrec_fresh_means"], literal["ligrec_fresh_pvalues"]
+    if ref_shim.available():  # the stored outputs are still what the literal source computes
+        df = pd.DataFrame(data, columns=list(range(g)))
+        df["clusters"] = pd.Categorical(cl)
+        ref = ref_shim.ligrec()["_analysis"](df, inter, cp, threshold=0.4, n_perms=40, seed=9, n_jobs=1, show_progress_bar=False)
+        np.testing.assert_array_equal(ref_means, ref.means)
+        np.testing.assert_array_equal(ref_pvalues, ref.pvalues)
     means, pvals = O.ligrec_analysis(data, cl, inter, cp, threshold=0.4, n_perms=40, seed=9)
-    np.testing.assert_array_equal(means, ref.means)
-    np.testing.assert_array_equal(pvals, ref.pvalues)
+    np.testing.assert_array_equal(means, ref_means)
+    np.testing.assert_array_equal(pvals, ref_pvalues)
     assert np.isnan(pvals).any() and (~np.isnan(pvals)).any()
 
 
@@ -215,7 +227,7 @@ def test_gene_symbols_are_swapped_in_and_restored(adata):
         ligrec(adata, "leiden", interactions=sym)
 
 
-def test_single_cluster_subset_is_computed_like_the_reference(adata, pairs):
+def test_single_cluster_subset_is_computed_like_the_reference(adata, pairs, literal):
     """`clusters=[("0", "0")]` resolves to ONE cluster: the reference's `_analysis` has no check and computes it
     (gr/_ligrec.py:677-775; only `<= 1` categories in `obs` are rejected, :300).  No device is needed: a constant label vector
     does not change under shuffling: every permuted mean is the kernel's sequential sum / size, which either exceeds pandas'
@@ -224,15 +236,20 @@ def test_single_cluster_subset_is_computed_like_the_reference(adata, pairs):
     assert res["pvalues"].shape == (len(res["means"]), 1)
     pv = res["pvalues"].to_numpy(dtype=np.float64)
     assert set(np.unique(pv[~np.isnan(pv)])) <= {0.0, 1.0}
-    if ref_shim.available():
-        genes = [g.upper() for g in dict.fromkeys(g for p in pairs for g in p)]
-        x = adata.raw.X.toarray()[:, :5]
-        keep = (adata.obs["leiden"].astype(str) == "0").to_numpy()
+    genes = [g.upper() for g in dict.fromkeys(g for p in pairs for g in p)]
+    x = adata.raw.X.toarray()[:, :5]
+    keep = (adata.obs["leiden"].astype(str) == "0").to_numpy()
+    gi = {g: i for i, g in enumerate(genes)}
+    inter = np.array([(gi[a], gi[b]) for a, b in res["means"].index], dtype=np.int32)
+    np.testing.assert_array_equal(x[keep], literal["ligrec_single_data"])
+    np.testing.assert_array_equal(inter, literal["ligrec_single_interactions"])
+    ref_means, ref_pvalues = literal["ligrec_single_means"], literal["ligrec_single_pvalues"]
+    if ref_shim.available():  # the stored outputs are still what the literal source computes
         df = pd.DataFrame(x[keep], columns=list(range(5)))
         df["clusters"] = pd.Categorical(np.zeros(int(keep.sum()), dtype=np.int32))
-        gi = {g: i for i, g in enumerate(genes)}
-        inter = np.array([(gi[a], gi[b]) for a, b in res["means"].index], dtype=np.int32)
         ref = ref_shim.ligrec()["_analysis"](df, inter, np.array([(0, 0)], dtype=np.int32), threshold=0.2, n_perms=7, seed=1, n_jobs=1,
                                            show_progress_bar=False)
-        np.testing.assert_array_equal(res["means"].to_numpy(dtype=np.float64), np.asarray(ref.means))
-        np.testing.assert_array_equal(pv, np.asarray(ref.pvalues))
+        np.testing.assert_array_equal(ref_means, np.asarray(ref.means))
+        np.testing.assert_array_equal(ref_pvalues, np.asarray(ref.pvalues))
+    np.testing.assert_array_equal(res["means"].to_numpy(dtype=np.float64), ref_means)
+    np.testing.assert_array_equal(pv, ref_pvalues)

@@ -168,23 +168,30 @@ def test_hex_graph_equals_gridbuilder_logic():
     assert (ref != O.hex_grid_graph(rows, cols)).nnz == 0
 
 
-@pytest.mark.skipif(not R.available(), reason="reference tree only exists in the build container")
 def test_restatement_equals_literal_source_on_fresh_inputs():
-    """Direct restate-vs-reference-source comparison on inputs that are not in the golden file."""
+    """Direct restate-vs-reference-source comparison on inputs that are not in the golden file (the literal source's outputs
+    are stored in tests/golden/literal_source_cases.npz by tests/golden/make_literal_source_golden.py)."""
+    lit = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "literal_source_cases.npz"))
     rng = np.random.default_rng(11)
     n, k = 120, 3
     A = sp.random(n, n, density=0.05, format="csr", random_state=5)
     labels = rng.integers(0, k, n).astype(np.uint32)
-    fn = R.nhood()["create_function"](k)
-    ref = fn(A.indices.astype(np.uint32), A.indptr.astype(np.uint32), labels)
+    np.testing.assert_array_equal(A.indices.astype(np.uint32), lit["nhood_indices"])
+    np.testing.assert_array_equal(A.indptr.astype(np.uint32), lit["nhood_indptr"])
+    np.testing.assert_array_equal(labels, lit["nhood_labels"])
+    ref = lit["nhood_count"]
+    if R.available():  # the stored outputs are still what the literal source computes
+        np.testing.assert_array_equal(R.nhood()["create_function"](k)(A.indices.astype(np.uint32), A.indptr.astype(np.uint32), labels), ref)
     np.testing.assert_array_equal(O.nhood_counts(A.indices, A.indptr, labels, k), ref)
-    pp = R.ppatterns()
     x, y = (rng.random(90) * 30).astype(np.float32), (rng.random(90) * 30).astype(np.float32)
     labs = rng.integers(0, k, 90).astype(np.int32)
     thr = (np.linspace(1, 20, 7, dtype=np.float32)) ** 2
-    np.testing.assert_array_equal(
-        O.occur_count(x, y, thr, labs, k), pp["_occur_count"](x, y, thr, labs, 90, k, len(thr))
-    )
+    for name, arr in (("x", x), ("y", y), ("thresholds", thr), ("labs", labs)):
+        np.testing.assert_array_equal(arr, lit[f"occur_{name}"], err_msg=name)
+    ref = lit["occur_counts"]
+    if R.available():
+        np.testing.assert_array_equal(R.ppatterns()["_occur_count"](x, y, thr, labs, 90, k, len(thr)), ref)
+    np.testing.assert_array_equal(O.occur_count(x, y, thr, labs, k), ref)
 
 
 def test_c_port_matches_golden(golden):

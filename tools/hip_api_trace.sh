@@ -8,14 +8,14 @@ OUT=$REPO/gpurun_out/hiptrace
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 cd $REPO
-timeout 900 rocprofv3 --hip-runtime-trace -d $OUT -o $TAG -- python bench.py --no-cpu-baseline --no-numpy-leg > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_err.log
+timeout 900 rocprofv3 --hip-runtime-trace -d $OUT -o $TAG -- python bench.py --full --no-cpu-baseline --no-numpy-leg > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_err.log
 python - $OUT $TAG <<'PY'
 import json, sqlite3, sys
 out, tag = sys.argv[1], sys.argv[2]
 d = json.loads(open(f"{out}/{tag}_bench.json").read().strip().splitlines()[-1])
 c = sqlite3.connect(f"{out}/{tag}_results.db")
 t0 = c.execute("select min(start) from regions").fetchone()[0]
-lines = [f"HIP API trace of `python bench.py --no-cpu-baseline --no-numpy-leg` (rocprofv3 --hip-runtime-trace), env SQGR_POOL_GB={__import__('os').environ.get('SQGR_POOL_GB', 'default')}",
+lines = [f"HIP API trace of `python bench.py --full --no-cpu-baseline --no-numpy-leg` (rocprofv3 --hip-runtime-trace), env SQGR_POOL_GB={__import__('os').environ.get('SQGR_POOL_GB', 'default')}",
          f"config 3 end to end (s): {d['legs'].get('config3_full')}; secondary: {d.get('secondary', {}).get('value')} genes/s, {d.get('secondary', {}).get('ms_per_step')} ms/step", "",
          "longest single calls:"]
 for name, start, dur in c.execute("select name, start, end - start from regions order by 3 desc limit 24"):

@@ -16,9 +16,9 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT $REPO/profiles
 cd /tmp && export TMPDIR=/tmp
-CMD="python $REPO/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-numpy-leg --no-legs --emulate-ranks 0 --detail-out $OUT/stats_detail.json"
-PMC="python $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-numpy-leg --no-legs --emulate-ranks 0 --detail-out $OUT/pmc_detail.json"
-LEGS="python $REPO/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-numpy-leg --no-secondary --no-short-radii --emulate-ranks 0 --detail-out $OUT/legs_detail.json"
+CMD="python $REPO/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-numpy-leg --no-legs --emulate-ranks 0 --detail-out $OUT/stats_detail.json"
+PMC="python $REPO/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-numpy-leg --no-legs --emulate-ranks 0 --detail-out $OUT/pmc_detail.json"
+LEGS="python $REPO/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-numpy-leg --no-secondary --no-short-radii --emulate-ranks 0 --detail-out $OUT/legs_detail.json"
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $CMD > $OUT/stats.log 2>&1
 timeout 900 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- $PMC > $OUT/fetch.log 2>&1
 timeout 900 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -- $PMC > $OUT/write.log 2>&1
@@ -33,7 +33,7 @@ timeout 900 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/legs_fetch --
 timeout 900 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/legs_write -- $LEGS > $OUT/legs_write.log 2>&1
 timeout 900 rocprofv3 --pmc TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCC_HIT_sum TCC_MISS_sum --output-format csv -d $OUT/legs_tcp -- $LEGS > $OUT/legs_tcp.log 2>&1
 # the numpy-stream shuffle (rng="numpy"): traffic of k_pcg_shuffle_wave
-NPY="python $REPO/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-secondary --no-legs --emulate-ranks 0 --detail-out $OUT/npy_detail.json"
+NPY="python $REPO/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-secondary --no-legs --emulate-ranks 0 --detail-out $OUT/npy_detail.json"
 timeout 900 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/npy_fetch -- $NPY > $OUT/npy_fetch.log 2>&1
 timeout 900 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/npy_write -- $NPY > $OUT/npy_write.log 2>&1
 # calibration of FETCH_SIZE / WRITE_SIZE on known byte counts, in the nhood kernels' access patterns
