@@ -365,6 +365,25 @@ int sqgr_ligrec_counts(sqgr_ctx* ctx, int64_t n_cells, int32_t n_genes, int32_t 
                        uint64_t seed, const uint64_t* pcg_states, int64_t perm_begin, int64_t perm_end, int64_t* out_counts,
                        double* out_means_perm0);
 
+/* ---- sepal: diffusion-time scores of spatially variable genes --------------------------------------------------------
+ * Replaces `_diffusion_genes` / `_diffusion` (gr/_sepal.py:165-251); the host builds the lattice of `_compute_idxs` (:308-363).
+ *   sat int32[n_sat]: the saturated spots (exactly max_neighs stored neighbours), nbr int32[n_sat][max_neighs] their neighbours in
+ *   the order the graph stores them (also the order of the neighbour sum); unsat int32[n_unsat] the other spots and src[q] the
+ *   POSITION in sat[] of unsat[q]'s nearest saturated spot.  n_sat + n_unsat == n, every spot exactly once; max_neighs 4 (square
+ *   grid, d2 = nbrs - 4c) or 6 (hex grid, d2 = (2 nbrs - 12c) / 3).
+ * sqgr_sepal_run: genes = columns cols[0 .. G) of m (n rows); out_iter[g] = the first sweep i with |ent_i - ent_{i-1}| <= thresh
+ *   (the reference's score is dt * i), -1 when no sweep within n_iter qualifies (NaN).  The concentrations follow numpy's bit for
+ *   bit; the entropy is a fixed-order float64 reduction, so a gene's result depends on that gene alone.
+ * sqgr_sepal_trace (parity hook): exactly n_steps sweeps of column col without a stop test; out_conc float64[n] the vector after
+ *   them, out_ent float64[n_steps] ent_i of every sweep; either may be NULL. */
+typedef struct sqgr_sepal sqgr_sepal;
+int sqgr_sepal_create(sqgr_ctx* ctx, int64_t n, int32_t max_neighs, const int32_t* sat, int64_t n_sat, const int32_t* nbr,
+                      const int32_t* unsat, const int32_t* src, int64_t n_unsat, sqgr_sepal** out);
+int sqgr_sepal_run(sqgr_sepal* h, const sqgr_matrix* m, const int32_t* cols, int64_t G, int32_t n_iter, double dt, double thresh,
+                   int32_t* out_iter);
+int sqgr_sepal_trace(sqgr_sepal* h, const sqgr_matrix* m, int32_t col, int32_t n_steps, double dt, double* out_conc, double* out_ent);
+int sqgr_sepal_destroy(sqgr_sepal* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,6 +94,10 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
         [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, c_i64p, c_i32p, c_f64p, c_i32p, c_f64p, c_i32p, C.c_int64, c_i32p, C.c_int32,
          c_f64p, c_u8p, C.c_uint64, c_u64p, C.c_int64, C.c_int64, c_i64p, c_f64p],
     ),
+    "sqgr_sepal_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, c_i32p, C.c_int64, c_i32p, c_i32p, c_i32p, C.c_int64, C.POINTER(C.c_void_p)]),
+    "sqgr_sepal_run": (C.c_int, [C.c_void_p, C.c_void_p, c_i32p, C.c_int64, C.c_int32, C.c_double, C.c_double, c_i32p]),
+    "sqgr_sepal_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, c_f64p, c_f64p]),
+    "sqgr_sepal_destroy": (C.c_int, [C.c_void_p]),
     "sqgr_cooccur_counts": (
         C.c_int,
         [C.c_void_p, c_f32p, c_f32p, c_i32p, C.c_int64, C.c_int32, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_i64p],
@@ -607,6 +611,50 @@ def cooccur_counts(
         ),
     )
     return out
+
+
+class SepalPlan:
+    """The lattice of ``sq.gr.sepal`` resident on the device (``sqgr_sepal``): the saturated spots ``sat`` with their neighbours
+    ``nbr`` (n_sat x max_neighs, stored order) and the unsaturated spots ``unsat`` with the position ``src`` in ``sat`` of their
+    nearest saturated spot (gr/_sepal.py:308-363).  ``run`` returns each gene's stop sweep (-1: none within ``n_iter``); ``trace``
+    runs a fixed number of sweeps of one gene and returns its vector and the entropy of every sweep (parity hook)."""
+
+    def __init__(self, ctx: Context, n: int, max_neighs: int, sat: np.ndarray, nbr: np.ndarray, unsat: np.ndarray, src: np.ndarray):
+        sat, nbr, unsat, src = _as(sat, np.int32), _as(nbr, np.int32), _as(unsat, np.int32), _as(src, np.int32)
+        if nbr.shape != (len(sat), int(max_neighs)) or len(src) != len(unsat):
+            raise ValueError(f"lattice shapes: sat {sat.shape}, nbr {nbr.shape}, unsat {unsat.shape}, src {src.shape}")
+        self.ctx, self.n, self.max_neighs = ctx, int(n), int(max_neighs)
+        h = C.c_void_p()
+        _check(ctx.lib, ctx.lib.sqgr_sepal_create(ctx.h, self.n, self.max_neighs, _ptr(sat, c_i32p), len(sat), _ptr(nbr, c_i32p),
+                                                  _ptr(unsat, c_i32p), _ptr(src, c_i32p), len(unsat), C.byref(h)))
+        self.h = h
+
+    def run(self, matrix: "DeviceMatrix", cols: np.ndarray, n_iter: int, dt: float, thresh: float) -> np.ndarray:
+        cols = _as(cols, np.int32)
+        out = np.empty(len(cols), dtype=np.int32)
+        matrix.wait_columns()
+        _check(self.ctx.lib, self.ctx.lib.sqgr_sepal_run(self.h, matrix.h, _ptr(cols, c_i32p), len(cols), int(n_iter), float(dt), float(thresh),
+                                                         _ptr(out, c_i32p)))
+        return out
+
+    def trace(self, matrix: "DeviceMatrix", col: int, n_steps: int, dt: float) -> tuple[np.ndarray, np.ndarray]:
+        conc = np.empty(self.n, dtype=np.float64)
+        ent = np.empty(int(n_steps), dtype=np.float64)
+        matrix.wait_columns()
+        _check(self.ctx.lib, self.ctx.lib.sqgr_sepal_trace(self.h, matrix.h, int(col), int(n_steps), float(dt), _ptr(conc, c_f64p),
+                                                           _ptr(ent, c_f64p) if n_steps > 0 else None))
+        return conc, ent
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            self.ctx.lib.sqgr_sepal_destroy(self.h)
+            self.h = None
+
+    def __del__(self) -> None:  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class DeviceMatrix:

@@ -15,6 +15,7 @@
 // is launched tile-major so that the ~N*512 B working set of the tiles in flight stays in the 256 MB Infinity Cache.
 // All reductions are two-stage with a fixed order => bit-reproducible run to run.
 #include "sqgr_common.h"
+#include "sqgr_matrix.h"
 #include "sqgr_rng.h"
 #include "sqgr_pcg.h"
 
@@ -1472,28 +1473,6 @@ __global__ void k_scores(int mode, int64_t G, int64_t n, double W, const double*
 
 using namespace sqgr;
 
-// The expression matrix resident on the device (uploaded once per call): dense row-major float64 / float32, or scipy's
-// CSR / CSC arrays as they are (int64 indptr, int32 indices; values float32 or float64).
-struct sqgr_matrix {
-    sqgr_ctx* ctx = nullptr;
-    int64_t n_rows = 0, n_cols = 0, ld = 0;
-    int kind = 0;        // 0 dense, 1 CSR (rows = cells), 2 CSC (columns = features)
-    bool f32 = false;    // values are float32
-    DevBuf<double> data;
-    DevBuf<float> data32;
-    DevBuf<int64_t> indptr;
-    DevBuf<int32_t> indices;
-    int64_t nnz = 0;
-    // CSR matrices: the same entries by column, built on the device the first time a column LIST is asked for (ensure_by_column)
-    int64_t cols_pending = -1;  // sqgr_matrix_alloc_dense: columns still to be uploaded (a streaming session is open while > 0)
-    mutable bool by_col_ready = false;
-    mutable DevBuf<int64_t> c_indptr;
-    mutable DevBuf<int32_t> c_rows;
-    mutable DevBuf<double> c_data;
-    mutable DevBuf<float> c_data32;
-    int ensure_by_column() const;
-};
-
 int sqgr_matrix::ensure_by_column() const {
     if (kind != 1 || by_col_ready) return SQGR_OK;
     hipStream_t st = ctx->stream;
@@ -1528,6 +1507,27 @@ int sqgr_matrix::ensure_by_column() const {
     by_col_ready = true;
     return SQGR_OK;
 }
+
+namespace sqgr {
+hipError_t expand_column_list(const sqgr_matrix* dm, const int32_t* dev_cols, int gc, double* X, hipStream_t st) {
+    const int64_t n = dm->n_rows;
+    if (dm->kind == 0) {
+        const dim3 tgrid((unsigned)ceil_div(n, GT), (unsigned)ceil_div(gc, GT));
+        if (dm->f32) k_cells_to_genes_idx<float><<<tgrid, 256, 0, st>>>(dm->data32.p, dm->ld, n, dev_cols, gc, X);
+        else k_cells_to_genes_idx<double><<<tgrid, 256, 0, st>>>(dm->data.p, dm->ld, n, dev_cols, gc, X);
+    } else {
+        const hipError_t e = hipMemsetAsync(X, 0, (size_t)gc * n * 8, st);
+        if (e != hipSuccess) return e;
+        const bool twin = dm->kind == 1;  // CSR: its by-column twin (ensure_by_column, called by the owner of the column list)
+        const int64_t* cp = twin ? dm->c_indptr.p : dm->indptr.p;
+        const int32_t* cr = twin ? dm->c_rows.p : dm->indices.p;
+        const dim3 cgrid(8, (unsigned)gc);
+        if (dm->f32) k_csc_to_genes_idx<float><<<cgrid, 256, 0, st>>>(cp, cr, twin ? dm->c_data32.p : dm->data32.p, n, dev_cols, X);
+        else k_csc_to_genes_idx<double><<<cgrid, 256, 0, st>>>(cp, cr, twin ? dm->c_data.p : dm->data.p, n, dev_cols, X);
+    }
+    return hipGetLastError();
+}
+}  // namespace sqgr
 
 struct sqgr_autocorr {
     sqgr_ctx* ctx = nullptr;
@@ -1869,21 +1869,7 @@ static int autocorr_create(sqgr_ctx* ctx, const sqgr_graph* g, const double* val
         const int gc = (int)std::min<int64_t>(gc_max, G - g0);
         if (dm && dev_cols) {  // a LIST of columns of the resident matrix
             LaunchTimer t(ctx, "autocorr_expand");
-            const dim3 tgrid((unsigned)ceil_div(n, GT), (unsigned)ceil_div(gc, GT));
-            if (dm->kind == 0) {
-                if (dm->f32) k_cells_to_genes_idx<float><<<tgrid, 256, 0, st>>>(dm->data32.p, dm->ld, n, dev_cols + g0, gc, X.p);
-                else k_cells_to_genes_idx<double><<<tgrid, 256, 0, st>>>(dm->data.p, dm->ld, n, dev_cols + g0, gc, X.p);
-            } else {
-                e = hipMemsetAsync(X.p, 0, (size_t)gc * n * 8, st);
-                if (e != hipSuccess) break;
-                const bool twin = dm->kind == 1;  // CSR: its by-column twin (built by the caller of this function)
-                const int64_t* cp = twin ? dm->c_indptr.p : dm->indptr.p;
-                const int32_t* cr = twin ? dm->c_rows.p : dm->indices.p;
-                const dim3 cgrid(8, (unsigned)gc);
-                if (dm->f32) k_csc_to_genes_idx<float><<<cgrid, 256, 0, st>>>(cp, cr, twin ? dm->c_data32.p : dm->data32.p, n, dev_cols + g0, X.p);
-                else k_csc_to_genes_idx<double><<<cgrid, 256, 0, st>>>(cp, cr, twin ? dm->c_data.p : dm->data.p, n, dev_cols + g0, X.p);
-            }
-            e = hipGetLastError();
+            e = expand_column_list(dm, dev_cols + g0, gc, X.p, st);
         } else if (dm && !dev_x) {  // float32 and / or sparse resident matrix: the gene block is formed from it on the device
             LaunchTimer t(ctx, "autocorr_expand");
             const dim3 tgrid((unsigned)ceil_div(n, GT), (unsigned)ceil_div(gc, GT));
