@@ -8,6 +8,10 @@
 // MI355X design: B (16 or 32) permutations are processed per pass over the graph.
 //   k_shuffle : thread per spot; B keyed Feistel bijections -> shuffled labels written as ONE B-byte
 //               row per spot: slab[spot][b] (uint8).  One 16/32-byte gather later serves B permutations.
+//   k_shuffle_tab : the same labels for 16-wide rows without libraries on up to 2^20 spots, at launch-group size: the first
+//               round of the per-permutation network depends on the spot only through the high digit of its group image, so
+//               each block tabulates it in LDS per row pair (64 KB) and a spot reads it back — 3 packed instructions per
+//               permutation pair instead of 10 (launch_shuffle_raw selects; SQGR_SHUFFLE_TABLE=0|1|2).
 //   k_count   : edge-parallel over the COO view (erow, indices); 4 lanes per edge, each lane owns B/4
 //               permutations; K*K*B counters live in LDS, laid out [pair][b] so that the 32 lanes of a
 //               DS lane group hit distinct banks (B=32) — ds_add_u32 without bank conflicts; block-local
@@ -290,6 +294,159 @@ __global__ __launch_bounds__(256) void k_shuffle(int64_t n, const uint32_t* __re
         slab_store16(slab_all + (size_t)row0 * n * 16, n, i, pw, outA[0], outA[1], outA[2], outA[3]);
         if (store1) slab_store16(slab_all + (size_t)row1 * n * 16, n, i, pw, outB[0], outB[1], outB[2], outB[3]);
     }
+    }
+}
+
+// k_shuffle<16, false, *> with sigma's FIRST round read from an LDS table (no libraries, A <= SHUF_TAB_MAX_A; selection:
+// launch_shuffle_raw).  All 16 permutations of a group start sigma from the same image (a, b) = pi_g(rank_i), and the first
+// round  b' = (b + F_B(a, k0_p)) mod B  takes from the spot only the high digit a < A ~ sqrt(n): k_shuffle evaluates F_B once per
+// (spot, permutation pair) — 1e6 x 8 evaluations per group for 1024 x 8 distinct values at n = 1e6.  Here every block builds
+//   T[g][a][t] = (F_B(a, k0 of permutation 2t) mod B) | (F_B(a, k0 of permutation 2t + 1) mod B) << 16,   g < 2, a < A, t < 8
+// (32 bytes per a and group, the packing of the sigma keys) for its row pair before the spot loop; a spot then reads its two rows
+// with two 16-byte LDS loads per group, and round 1 of a pair is add / subtract / min: the stored value is < B, so b + T < 2B <=
+// 2^15 has no 16-bit carry and ONE conditional subtraction reduces it — the same b' as the two subtractions of b + F_B, since
+// (b + F) mod B == (b + (F mod B)) mod B (tests/test_shuffle_table_cpu.py).  10 packed instructions per pair become 3; round 2,
+// the block-table look-up, the sentinel test and the exact route are k_shuffle's (the exact route re-walks sigma with the real
+// keys, which it loads itself: the 16 k0 words are not live in the spot loop).  1024-thread blocks, two per CU (2 x 69 KB of LDS
+// at A = 1024): <= 64 VGPRs.  LDS: [blk_words] block table at byte offset 0, [kpad] boundaries, then T at word tab_word0.
+constexpr int SHUF_TAB_THREADS = 1024;
+constexpr uint32_t SHUF_TAB_MAX_A = 1024;  // 2 groups x A x 32 bytes = 64 KB: two blocks per CU
+constexpr int SHUF_TAB_BLOCKS_PER_CU = 20;  // grid cap (launch_shuffle_raw)
+constexpr int SHUF_TAB_MIN_TRIPS = 16;      // automatic selection: spots per thread of a resident block (launch_shuffle_raw)
+template <bool SMALLK>
+__global__ __launch_bounds__(SHUF_TAB_THREADS, 8) void k_shuffle_tab(int64_t n, const uint32_t* __restrict__ cum, int kpad, int blk_words, int K,
+                                                                  const uint32_t* __restrict__ keys, LibDom dom0, int nrows,
+                                                                  uint8_t* __restrict__ slab_all, int pw, const int32_t* __restrict__ spot_of,
+                                                                  int tab_word0) {
+    extern __shared__ uint32_t s_lds[];
+    uint32_t* s_cum = s_lds + blk_words;
+    for (int t = threadIdx.x; t < kpad; t += SHUF_TAB_THREADS) s_cum[t] = cum[t];
+    for (int t = threadIdx.x; t < blk_words; t += SHUF_TAB_THREADS) s_lds[t] = cum[kpad + t];
+    const FeistelDomain dom = dom0.dom;
+    const int row0 = 2 * blockIdx.y;
+    const int row1 = min(row0 + 1, nrows - 1);  // an odd last row is paired with itself (stored once)
+    const bool store1 = row0 + 1 < nrows;
+    constexpr size_t row_words = key_words_per_row(16, 1);
+    const uint32_t* kgA = keys + (size_t)row0 * row_words;  // group keys, then the sigma keys of the group's 8 pairs
+    const uint32_t* kgB = keys + (size_t)row1 * row_words;
+    const uint32_t* ksA = kgA + 8;
+    const uint32_t* ksB = kgB + 8;
+    const u16x2 BB = (u16x2)((unsigned short)dom.B);
+    {   // the two tables of this row pair: F_B <= Bmask < 2B, one conditional subtraction stores it mod B
+        const u16x2 bsh = (u16x2)((unsigned short)dom.bsh);
+        const int words = (int)dom.A * 8;
+        for (int idx = threadIdx.x; idx < words; idx += SHUF_TAB_THREADS) {
+            const u16x2 av = (u16x2)((unsigned short)(idx >> 3));
+            const int t = idx & 7;
+            u16x2 fa = feistel_F2(av, __builtin_bit_cast(u16x2, ksA[t * 2]), bsh);
+            u16x2 fb = feistel_F2(av, __builtin_bit_cast(u16x2, ksB[t * 2]), bsh);
+            fa = __builtin_elementwise_min(fa, (u16x2)(fa - BB));
+            fb = __builtin_elementwise_min(fb, (u16x2)(fb - BB));
+            s_lds[tab_word0 + idx] = __builtin_bit_cast(uint32_t, fa);
+            s_lds[tab_word0 + words + idx] = __builtin_bit_cast(uint32_t, fb);
+        }
+    }
+    __syncthreads();
+    const uint32_t zero = 0;
+    const uint32_t sent_add = (uint32_t)(128 - K) * 0x01010101u;
+    const uint32_t* tab = s_cum + 1;  // tab[k] = cum[k + 1]
+    typedef __attribute__((address_space(3))) const uint32_t lds_word;
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(3))) const u32x4 lds_row;
+    auto blk_at = [&](uint32_t byte_off) { return *reinterpret_cast<lds_word*>((uintptr_t)byte_off); };
+    const uint32_t tabA = (uint32_t)tab_word0 * 4u, tabB = tabA + dom.A * 32u;  // byte offsets (multiples of 32)
+    const u16x2 am = (u16x2)((unsigned short)(dom.A - 1u));
+    const u16x2 ash = (u16x2)((unsigned short)dom.ash);
+    for (int64_t i = blockIdx.x * (int64_t)SHUF_TAB_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * SHUF_TAB_THREADS) {
+    const uint32_t x0 = spot_of ? (uint32_t)spot_of[i] : (uint32_t)i;
+    const uint32_t a0 = x0 / dom.B, b0 = x0 - a0 * dom.B;
+    // pi_gA (low halves) and pi_gB (high halves) in one packed evaluation; cycle walk per half (k_shuffle)
+    u16x2 ga = (u16x2)((unsigned short)a0), gb = (u16x2)((unsigned short)b0);
+    {
+        uint32_t kp[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) kp[r] = (kgA[r] & 0xFFFFu) | (kgB[r] & 0xFFFF0000u);
+        const uint32_t* const pg[1] = {kp};
+        bool need0 = true, need1 = true;
+        do {
+            u16x2 na[1] = {ga}, nb[1] = {gb};
+            feistel_rounds<1>(na, nb, dom, pg);
+            if (need0) { ga.x = na[0].x; gb.x = nb[0].x; }
+            if (need1) { ga.y = na[0].y; gb.y = nb[0].y; }
+            need0 = __umul24((uint32_t)ga.x, dom.B) + (uint32_t)gb.x >= dom.n;
+            need1 = __umul24((uint32_t)ga.y, dom.B) + (uint32_t)gb.y >= dom.n;
+        } while (need0 | need1);
+    }
+    // the 16 labels of one group: round 1 of sigma_p from the table row of the group image's high digit, round 2 as in k_shuffle
+    auto emit_group = [&](const u16x2 gsa, const u16x2 gsb, const uint32_t row_off, const uint32_t* ks, uint32_t (&out)[4]) {
+        const u32x4 r0 = *reinterpret_cast<lds_row*>((uintptr_t)row_off);
+        const u32x4 r1 = *reinterpret_cast<lds_row*>((uintptr_t)(row_off + 16u));
+        const uint32_t f1[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+#pragma unroll
+        for (int w = 0; w < FEISTEL_GROUP / 4; ++w) {
+            uint32_t word = 0;
+            uint32_t apk[2], bpk[2];  // sigma images of the word's two pairs (kept for the exact route)
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj) {
+                const u16x2 t = gsb + __builtin_bit_cast(u16x2, f1[w * 2 + jj]);
+                const u16x2 b = __builtin_elementwise_min(t, (u16x2)(t - BB));
+                const u16x2 k1 = __builtin_bit_cast(u16x2, ks[(w * 2 + jj) * 2 + 1]);
+                const u16x2 a = (gsa + feistel_F2(b, k1, ash)) & am;
+                apk[jj] = __builtin_bit_cast(uint32_t, a);
+                bpk[jj] = __builtin_bit_cast(uint32_t, b);
+                const uint32_t a4 = apk[jj] << 2;  // both halves at once (a < 2^14): byte offsets into the block table
+                const uint32_t e0 = blk_at(a4 & 0xFFFFu);
+                const uint32_t e1 = blk_at(a4 >> 16);
+                if (jj == 0) {
+                    put_label<0, 0>(word, e0, bpk[jj], zero);
+                    put_label<1, 1>(word, e1, bpk[jj], zero);
+                } else {
+                    put_label<2, 0>(word, e0, bpk[jj], zero);
+                    put_label<3, 1>(word, e1, bpk[jj], zero);
+                }
+            }
+            bool sentinel;
+            if constexpr (SMALLK) {
+                sentinel = ((word + sent_add) & 0x80808080u) != 0;
+            } else {  // K = 256 has no sentinel value left in a byte: every label takes the exact route
+                const uint32_t k = (uint32_t)K;
+                sentinel = k > 255u || (word & 0xFFu) >= k || ((word >> 8) & 0xFFu) >= k || ((word >> 16) & 0xFFu) >= k || (word >> 24) >= k;
+            }
+            if (sentinel) {  // exact route (rare), k_shuffle's: re-walk sigma with the real keys where the image left [0, n)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (K <= 255 && ((word >> (8 * j)) & 0xFFu) < (uint32_t)K) continue;
+                    const int jj = j >> 1, sh = (j & 1) * 16;
+                    const uint32_t* sk = ks + (w * 2 + jj) * 2;
+                    uint32_t a = (apk[jj] >> sh) & 0xFFFFu, b = (bpk[jj] >> sh) & 0xFFFFu;
+                    uint32_t x = a * dom.B + b;
+                    if (x >= dom.n) {
+                        const uint32_t k0 = (sk[0] >> sh) & 0xFFFFu, k1 = (sk[1] >> sh) & 0xFFFFu;
+                        do {
+                            uint32_t t = b + feistel_F1(a, k0, dom.bsh);
+                            t = t >= dom.B ? t - dom.B : t;
+                            b = t >= dom.B ? t - dom.B : t;
+                            a = (a + feistel_F1(b, k1, dom.ash)) & (dom.A - 1u);
+                            x = a * dom.B + b;
+                        } while (x >= dom.n);
+                    }
+                    const uint32_t e = blk_at(a * 4u);  // the table again: nearly always enough
+                    uint32_t l = (e & 0xFFFFu) + (b >= (e >> 16) ? 1u : 0u);
+                    if (l >= (uint32_t)K) {  // a block the two-field form cannot describe: rank against the boundaries
+                        l = K <= 255 ? (e >> 8) & 0xFFu : 0u;
+                        while (x >= tab[l]) ++l;  // sentinel UINT_MAX stops it
+                    }
+                    word = (word & ~(0xFFu << (8 * j))) | (l << (8 * j));
+                }
+            }
+            out[w] = word;
+        }
+    };
+    uint32_t outA[4], outB[4];
+    emit_group((u16x2)(ga.x), (u16x2)(gb.x), tabA + (uint32_t)ga.x * 32u, ksA, outA);
+    if (store1) emit_group((u16x2)(ga.y), (u16x2)(gb.y), tabB + (uint32_t)ga.y * 32u, ksB, outB);
+    slab_store16(slab_all + (size_t)row0 * n * 16, n, i, pw, outA[0], outA[1], outA[2], outA[3]);
+    if (store1) slab_store16(slab_all + (size_t)row1 * n * 16, n, i, pw, outB[0], outB[1], outB[2], outB[3]);
     }
 }
 
@@ -2251,7 +2408,54 @@ static int launch_shuffle_raw(sqgr_nhood* p, int B, int nb, const uint32_t* keys
         return SQGR_OK;
     }
     const unsigned gy = (unsigned)(B == 32 ? nb : (nb + 1) / 2);  // 16-permutation rows are shuffled in pairs
-#define SQGR_SHUFFLE(BB, LIBS, SK)                                                                                               \
+    {   // k_shuffle_tab: sigma's first round from an LDS table.  SQGR_SHUFFLE_TABLE (read at every call): 0 never, 1 whenever the
+        // input is eligible, 2 required (an input that is not eligible is an error that names the reason), unset: automatic
+        const char* env_tab = getenv("SQGR_SHUFFLE_TABLE");
+        const int mode = env_tab ? atoi(env_tab) : -1;
+        const uint32_t A = p->dom0.dom.A;
+        const size_t tab_word0 = (lds / 4 + 7) & ~(size_t)7;  // 32-byte rows behind the block table and the boundaries
+        const size_t lds_tab = tab_word0 * 4 + (size_t)2 * A * 32;
+        const char* why = nullptr;
+        if (B != 16) why = "32 permutations per row";
+        else if (p->has_libs) why = "libraries (per-library domains and keys)";
+        else if (A > SHUF_TAB_MAX_A) why = "more than 2^20 spots (high digit A > 1024: the two tables exceed 64 KB)";
+        else if (lds_tab > LDS_BUDGET / 2) why = "tables do not fit two blocks per CU";
+        if (mode == 2 && why) {
+            set_error("SQGR_SHUFFLE_TABLE=2: the table kernel does not take this input: %s", why);
+            return SQGR_ERR_UNSUPPORTED;
+        }
+        // automatic: launches of at least SHUF_TAB_MIN_TRIPS spots per thread of a resident block (two per CU) — smaller ones cannot
+        // both fill the CUs and amortise the table build (16 packed evaluations per thread at A = 1024, about a third of a spot's
+        // work) and keep k_shuffle.  Measured on MI355X, ms per launch, k_shuffle | k_shuffle_tab, 30 clusters — 1e6 spots: 16 rows
+        // (7.6 trips) 0.137 | 0.158, 32 rows (15) 0.260 | 0.252, 64 rows 0.508 | 0.453, 160 rows 1.284 | 1.059; 105 600 spots
+        // (A = 512): 64 rows (6.5 trips) 0.091 | 0.091, 160 rows (16) 0.202 | 0.193.
+        const int cus = std::max(p->ctx->cu_count, 1);
+        const int64_t block_trips = ceil_div(p->n, SHUF_TAB_THREADS) * (int64_t)gy;  // (block, trip) units of the launch
+        const bool big = block_trips >= (int64_t)SHUF_TAB_MIN_TRIPS * 2 * cus;
+        if (!why && mode != 0 && (mode == 1 || mode == 2 || big)) {
+            int tab_per_cu = SHUF_TAB_BLOCKS_PER_CU;
+            if (env_blocks && atoi(env_blocks) > 0) tab_per_cu = atoi(env_blocks);
+            // grid cap as for k_shuffle, then the same number of trips for every block (105 600 spots x 160 rows: 104 blocks' worth
+            // of spots on 65 blocks — some walk two trips, some one — 0.214 ms; on 52 blocks of two trips each 0.193).  1e6 spots x
+            // 160 rows by the cap: 6 blocks per CU 1.168 ms, 8: 1.134, 12: 1.076, 16: 1.063, 20: 1.062, 32: 1.060, 48: 1.078, 96: 1.179
+            const unsigned nblk = (unsigned)ceil_div(p->n, SHUF_TAB_THREADS);
+            const unsigned cap = (unsigned)(tab_per_cu * cus) / gy + 1;
+            const unsigned trips = (nblk + cap - 1) / cap;
+            const unsigned tx = (nblk + trips - 1) / trips;
+            if (p->K <= 126) {
+                SQGR_TRY(allow_lds(k_shuffle_tab<true>, lds_tab));
+                k_shuffle_tab<true><<<dim3(tx, gy), SHUF_TAB_THREADS, lds_tab, st>>>(p->n, p->cum.p, p->kpad, p->blk_bytes, p->K, keys, p->dom0, nb, slab, pw,
+                                                                                   p->spot_of.p, (int)tab_word0);
+            } else {
+                SQGR_TRY(allow_lds(k_shuffle_tab<false>, lds_tab));
+                k_shuffle_tab<false><<<dim3(tx, gy), SHUF_TAB_THREADS, lds_tab, st>>>(p->n, p->cum.p, p->kpad, p->blk_bytes, p->K, keys, p->dom0, nb, slab, pw,
+                                                                                    p->spot_of.p, (int)tab_word0);
+            }
+            SQGR_HIP(hipGetLastError());
+            return SQGR_OK;
+        }
+    }
+#define SQGR_SHUFFLE(BB, LIBS, SK)                                                                                             \
     k_shuffle<BB, LIBS, SK><<<dim3(gx, gy), 256, lds, st>>>(p->n, p->cum.p, p->kpad, p->blk_bytes, p->K, keys, p->dom0, p->n_libs, nb, \
                                                             p->lib_of.p, p->rank_of.p, p->libs.p, slab, pw, p->spot_of.p)
 #define SQGR_SHUFFLE_K(BB, LIBS) \
