@@ -117,6 +117,13 @@ int sqgr_graph_destroy(sqgr_graph* g);
  * order)` returns exactly the moments of the plan on the caller's own graph (sqgr_nhood_run; ABI v7). */
 int sqgr_graph_renumbered(sqgr_ctx* ctx, const sqgr_graph* g, const int32_t* order, sqgr_graph** out_graph);
 int sqgr_spatial_order(sqgr_ctx* ctx, const double* xy, int64_t n, int32_t* out_order);
+/* The segment list of a structurally symmetric graph without self loops (lattices in scan order: the count kernel of the permutation
+ * test walks 16 consecutive rows with one column offset as one entry; SQGR_COUNT_SEGMENTS, ABI v7), built on first use; for tests.
+ *   out_info: int64[5] = {1 built | 0 not applicable (sqgr_last_error names the reason; the call still returns SQGR_OK), entries,
+ *             entries with the zero-mask padding, residual half edges, half edges}
+ *   out_seg:  int32[padded entries][3] = (r0, d, mask) or NULL — bit j of mask <=> half edge (r0 + j, r0 + j + d); ordered by (r0, d)
+ *   out_res:  int32[residual][2] = (r, c) or NULL — the half edges of the entries with fewer than 8 edges. */
+int sqgr_graph_segments(const sqgr_graph* g, int64_t* out_info, int32_t* out_seg, int32_t* out_res);
 
 /* ------------------------------------------------------------------ nhood_enrichment
  * replaces the generated numba kernel `_nenrich_{K}_{parallel}` (gr/_nhood.py:54-141):

@@ -52,6 +52,7 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "sqgr_graph_destroy": (C.c_int, [C.c_void_p]),
     "sqgr_graph_renumbered": (C.c_int, [C.c_void_p, C.c_void_p, c_i32p, C.POINTER(C.c_void_p)]),
     "sqgr_spatial_order": (C.c_int, [C.c_void_p, c_f64p, C.c_int64, c_i32p]),
+    "sqgr_graph_segments": (C.c_int, [C.c_void_p, c_i64p, c_i32p, c_i32p]),
     "sqgr_nhood_set_spot_map": (C.c_int, [C.c_void_p, c_i32p]),
     "sqgr_nhood_counts": (C.c_int, [C.c_void_p, C.c_void_p, c_i32p, C.c_int32, c_u32p]),
     "sqgr_nhood_counts_batch": (C.c_int, [C.c_void_p, C.c_void_p, c_u8p, C.c_int64, C.c_int32, c_u32p]),
@@ -348,6 +349,19 @@ class Graph:
             self._twin[1].close()
         self._twin = (order.copy(), twin)
         return twin
+
+    def segments(self) -> "tuple[np.ndarray, np.ndarray, int] | None":
+        """The segment list the permutation test's count kernel walks on lattice graphs (``sqgr_graph_segments``):
+        ``(entries int32 (padded, 3) = (r0, d, mask), residual half edges int32 (m, 2) = (r, c), entries without the padding)``, or
+        ``None`` where the graph has none (not structurally symmetric, self loops)."""
+        info = np.zeros(5, dtype=np.int64)
+        _check(self.ctx.lib, self.ctx.lib.sqgr_graph_segments(self.h, _ptr(info, c_i64p), None, None))
+        if not info[0]:
+            return None
+        seg = np.zeros((int(info[2]), 3), dtype=np.int32)
+        res = np.zeros((int(info[3]), 2), dtype=np.int32)
+        _check(self.ctx.lib, self.ctx.lib.sqgr_graph_segments(self.h, _ptr(info, c_i64p), _ptr(seg, c_i32p), _ptr(res, c_i32p)))
+        return seg, res, int(info[1])
 
     def close(self) -> None:
         if getattr(self, "_twin", None) is not None:

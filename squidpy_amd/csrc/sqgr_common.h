@@ -206,6 +206,13 @@ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // STEP = 4096 edges per iteration of a block), plus a lane's own four edges.  (Round 5 padded six: ADVICE r5, a third of all graph
 // sizes read up to 30 KB past the allocation — values never consumed, but an out-of-bounds read all the same.)
 constexpr int LIST_PAD = 7 * 4096 + 64;
+// segment list of a lattice graph (sqgr_graph::ensure_seg, k_count_seg): entries of fewer edges stay edges; entries a block of 16 waves
+// takes per iteration; zero-mask entries behind the list — the sweep of a chunk of T iterations loads up to T + 6 iterations from its start
+constexpr int SEG_MIN_FILL = 8;
+constexpr int SEG_ITER = 64;
+constexpr int SEG_PAD = 8 * SEG_ITER;
+// bytes k_count_seg may read past a batch's 16 n slab bytes: rows r0 + j (+ d) of absent edges, up to 15 rows past the last spot
+constexpr int SEG_SLAB_PAD = 256;
 
 // device-side collectives of an sqgr_comm (sqgr_comm.hip); no-ops for a NULL communicator or a single rank
 int comm_allreduce_i64_dev(sqgr_comm* c, int64_t* dev_buf, size_t count, bool op_max, hipStream_t st);
@@ -247,6 +254,27 @@ struct sqgr_graph {
     mutable int64_t n_mutual = 0;  // mutual pairs (edges with r < c that have a mirror)
     mutable int64_t n_oneway = 0;  // edges without a mirror
     int ensure_split() const;
+    // Lattice graphs in scan order (every coord_type="grid" graph): the half list has a handful of distinct offsets d = c - r, so
+    // for 16 consecutive rows r0 .. r0 + 15 and one d both endpoints' label rows are 256 CONTIGUOUS slab bytes — k_count_seg
+    // (sqgr_nhood.hip) loads each side with one coalesced dword load per wave instead of a 16-row gather.  The half list of a
+    // symmetric graph without self loops is cut by (r >> 4, d) into entries (r0, d, mask): bit j of mask <=> edge (r0 + j,
+    // r0 + j + d) exists.  Entries with at least SEG_MIN_FILL edges (and d < 2^16: d and the mask share a word) go to `seg`, ordered
+    // by (r0, d); every other half edge goes to `seg_res`, a residual list in the (16 r, 16 c) format of `half` with LIST_PAD.
+    // `seg` holds GROUPS of four entries, what a wave consumes per iteration, in 8 words: {16 r0 of the four entries, d0 | d1 << 16,
+    // d2 | d3 << 16, mask0 | mask1 << 16, mask2 | mask3 << 16}; behind the n_seg entries zero-mask entries up to a multiple of
+    // SEG_ITER plus SEG_PAD more, so that a block's chunk is whole iterations and the kernel's look-ahead never clamps.
+    // seg_coverage() counts the half edges the segments would hold (n_seg_edges) on the CSR, one pass without the list: what the
+    // automatic rule needs to turn a graph down before it pays for the build.
+    // seg_state: 0 not built (not tried, not wanted, or the build failed: a later call tries again), 1 built, -1 not applicable (not symmetric, self loops, 16 n + 256 bytes of slab offsets pass 2^32).
+    mutable int seg_state = 0;
+    mutable const char* seg_why = nullptr;  // seg_state == -1: the reason
+    mutable sqgr::DevBuf<uint32_t> seg;     // [(n_seg_padded / 4) * 8]
+    mutable sqgr::DevBuf<int2> seg_res;     // [n_seg_res + LIST_PAD]
+    mutable int64_t n_seg = 0, n_seg_padded = 0, n_seg_edges = 0, n_seg_res = 0;
+    mutable bool seg_cov_known = false;
+    int seg_coverage() const;
+    int ensure_seg() const;
+    int build_seg() const;  // ensure_seg's fallible part
     // The pass kernel of the permutation test (51 <= K <= 202 clusters, sqgr_nhood.hip: k_count_pass) reads the SAME list in
     // another order and with other offsets: inside every aligned group of 4*J entries (J = 32 | 64 edge slots of a wavefront)
     // slot j of gather instruction u = 0..3 — physical position 4*j + u — holds the list's entry (u/R)*(J*R) + j*R + u%R, so

@@ -465,6 +465,93 @@ __global__ __launch_bounds__(256) void k_tile_keys(const int2* __restrict__ list
     keys[e] = (rb << 31) | cb;
 }
 
+// segment list (sqgr_graph::ensure_seg).  Key of a half edge (16 r, 16 c), d = c - r < 2^28: (r >> 4) << 32 | d << 4 | r & 15 — a radix
+// sort puts the at most 16 edges of an entry (r >> 4, d) next to each other, in row order
+__global__ __launch_bounds__(256) void k_seg_keys(const int2* __restrict__ half, uint32_t m, uint64_t* __restrict__ keys) {
+    const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+    if (e >= m) return;
+    const int2 rc = half[e];
+    const uint32_t r = (uint32_t)rc.x >> 4, d = ((uint32_t)rc.y >> 4) - r;
+    keys[e] = ((uint64_t)(r >> 4) << 32) | ((uint64_t)d << 4) | (r & 15u);
+}
+
+// per sorted key: the mask of its entry (its run of equal key >> 4: at most 15 keys to either side).  The run's first key emits the
+// entry (16 r0, mask << 16 | d) when it is dense; every key of a run that is not emits its edge (16 r, 16 c).
+__global__ __launch_bounds__(256) void k_seg_classify(const uint64_t* __restrict__ keys, uint32_t m, uint64_t* __restrict__ seg_item,
+                                                      uint64_t* __restrict__ res_item, uint8_t* __restrict__ seg_flag,
+                                                      uint8_t* __restrict__ res_flag) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= m) return;
+    const uint64_t k = keys[i], run = k >> 4;
+    uint32_t mask = 1u << (uint32_t)(k & 15u);
+    bool head = true;
+    for (uint32_t j = 1; j < 16 && j <= i; ++j) {
+        const uint64_t o = keys[i - j];
+        if ((o >> 4) != run) break;
+        mask |= 1u << (uint32_t)(o & 15u);
+        head = false;
+    }
+    for (uint32_t j = 1; j < 16 && i + j < m; ++j) {
+        const uint64_t o = keys[i + j];
+        if ((o >> 4) != run) break;
+        mask |= 1u << (uint32_t)(o & 15u);
+    }
+    const uint32_t d = (uint32_t)(run & 0x0fffffffu), r0 = (uint32_t)(k >> 32) << 4, r = r0 + (uint32_t)(k & 15u);
+    const bool dense = __popc(mask) >= SEG_MIN_FILL && d < 65536u;
+    seg_flag[i] = head && dense;
+    res_flag[i] = !dense;
+    seg_item[i] = (uint64_t)(16u * r0) | ((uint64_t)((mask << 16) | (d & 0xffffu)) << 32);
+    res_item[i] = (uint64_t)(16u * r) | ((uint64_t)(16u * (r + d)) << 32);  // int2 (x = 16 r, y = 16 c)
+}
+
+// coverage of the segment list WITHOUT building it: a half edge (r, r + d) lies in a dense entry iff at least SEG_MIN_FILL of the 16
+// rows of its group hold column (row + d) — fifteen binary searches in the canonical CSR per half edge, no sort, no workspace
+__global__ __launch_bounds__(256) void k_seg_coverage(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
+                                                      const int32_t* __restrict__ erow, int64_t nnz, int64_t n,
+                                                      unsigned long long* __restrict__ covered) {
+    const int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    bool dense = false;
+    if (e < nnz) {
+        const int64_t r = erow[e], c = indices[e], d = c - r;
+        if (d > 0 && d < 65536) {
+            int fill = 1;
+            const int64_t r0 = r & ~(int64_t)15;
+            for (int j = 0; j < 16; ++j) {
+                const int64_t rr = r0 + j, cc = rr + d;
+                if (rr == r || cc >= n) continue;
+                int64_t lo = indptr[rr], hi = indptr[rr + 1];
+                const int64_t end = hi;
+                while (lo < hi) {
+                    const int64_t mid = (lo + hi) >> 1;
+                    if (indices[mid] < cc) lo = mid + 1; else hi = mid;
+                }
+                fill += (lo < end && indices[lo] == cc) ? 1 : 0;
+            }
+            dense = fill >= SEG_MIN_FILL;
+        }
+    }
+    const uint64_t m = __ballot(dense);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(covered, (unsigned long long)__popcll(m));
+}
+
+// groups of four entries in the kernel's layout (sqgr_common.h); zero-mask entries behind the list
+__global__ __launch_bounds__(256) void k_seg_pack(const uint64_t* __restrict__ ent, uint32_t n_seg, uint32_t groups, uint32_t* __restrict__ out) {
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= groups) return;
+    uint32_t w0[4], w1[4];
+    for (uint32_t u = 0; u < 4; ++u) {
+        const uint64_t v = 4 * g + u < n_seg ? ent[4 * g + u] : 0;
+        w0[u] = (uint32_t)v;
+        w1[u] = (uint32_t)(v >> 32);
+    }
+    uint32_t* o = out + (size_t)g * 8;
+    for (uint32_t u = 0; u < 4; ++u) o[u] = w0[u];
+    o[4] = (w1[0] & 0xffffu) | (w1[1] << 16);
+    o[5] = (w1[2] & 0xffffu) | (w1[3] << 16);
+    o[6] = (w1[0] >> 16) | (w1[1] & 0xffff0000u);
+    o[7] = (w1[2] >> 16) | (w1[3] & 0xffff0000u);
+}
+
 }  // namespace sqgr
 
 using namespace sqgr;
@@ -595,6 +682,106 @@ int sqgr_graph::ensure_split() const {
     n_mutual = (int64_t)m;
     n_oneway = (int64_t)o;
     split_state = 1;
+    return SQGR_OK;
+}
+
+int sqgr_graph::seg_coverage() const {
+    if (seg_cov_known || seg_state == -1) return SQGR_OK;
+    SQGR_TRY(ensure_half());
+    const char* why = nullptr;
+    if (sym_state != 1) why = "the graph is not structurally symmetric (no half list)";
+    else if (n_self > 0) why = "the graph has self loops";
+    else if (n_half == 0) why = "the graph has no edges";
+    else if (16 * n + SEG_SLAB_PAD >= ((int64_t)1 << 32)) why = "slab offsets of the segment rows pass 32 bits";
+    if (why) {  // (decided without a fallible step: a graph is marked "no list" only together with its reason)
+        seg_why = why;
+        seg_state = -1;
+        return SQGR_OK;
+    }
+    SQGR_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    DevBuf<unsigned long long> covered;
+    SQGR_TRY(covered.alloc(1));
+    SQGR_HIP(hipMemsetAsync(covered.p, 0, 8, st));
+    unsigned long long h_cov = 0;
+    {
+        LaunchTimer t(ctx, "graph_seg_coverage");
+        k_seg_coverage<<<(unsigned)ceil_div(nnz, 256), 256, 0, st>>>(indptr.p, indices.p, erow.p, nnz, n, covered.p);
+        SQGR_HIP(hipGetLastError());
+    }
+    SQGR_HIP(hipMemcpyAsync(&h_cov, covered.p, 8, hipMemcpyDeviceToHost, st));
+    SQGR_HIP(hipStreamSynchronize(st));
+    n_seg_edges = (int64_t)h_cov;
+    seg_cov_known = true;
+    return SQGR_OK;
+}
+
+// A failure on the way (out of memory for the workspace, most likely) leaves seg_state at 0 and the graph without a list: the call
+// returns the error, a later call tries again, and a plan in automatic mode runs k_count on the half list as it always did.
+int sqgr_graph::ensure_seg() const {
+    if (seg_state != 0) return SQGR_OK;
+    SQGR_TRY(seg_coverage());
+    if (seg_state != 0) return SQGR_OK;
+    const int rc = build_seg();
+    if (rc != SQGR_OK) {
+        seg.release();
+        seg_res.release();
+        n_seg = n_seg_padded = n_seg_res = 0;
+        return rc;
+    }
+    seg_state = 1;
+    return SQGR_OK;
+}
+
+int sqgr_graph::build_seg() const {
+    if (const char* e = getenv("SQGR_SEG_FAIL_BUILD"); e && atoi(e)) {  // tests: a build that fails as an allocation would
+        set_error("the segment list build failed on request (SQGR_SEG_FAIL_BUILD)");
+        return SQGR_ERR_NOMEM;
+    }
+    SQGR_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint32_t m = (uint32_t)n_half;
+    // one allocation for the five 8-byte arrays, the two flag arrays and the two counts (a first call pays every hipMalloc)
+    DevBuf<uint64_t> ws;
+    DevBuf<uint8_t> tmp;
+    const size_t flag_words = ((size_t)m + 7) / 8;
+    SQGR_TRY(ws.alloc((size_t)5 * m + 2 * flag_words + 1));
+    uint64_t *keys = ws.p, *sorted = keys + m, *seg_item = sorted + m, *res_item = seg_item + m, *seg_out = res_item + m;
+    uint8_t* seg_flag = reinterpret_cast<uint8_t*>(seg_out + m);
+    uint8_t* res_flag = seg_flag + flag_words * 8;
+    int* counts = reinterpret_cast<int*>(res_flag + flag_words * 8);
+    LaunchTimer t(ctx, "graph_seg_list");
+    k_seg_keys<<<(unsigned)ceil_div(m, 256), 256, 0, st>>>(half.p, m, keys);
+    SQGR_HIP(hipGetLastError());
+    size_t sort_bytes = 0, sel_bytes = 0;
+    SQGR_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, keys, sorted, (int)m, 0, 56, st));
+    SQGR_HIP(hipcub::DeviceSelect::Flagged(nullptr, sel_bytes, seg_item, seg_flag, seg_out, counts, (int)m, st));
+    SQGR_TRY(tmp.alloc(std::max(sort_bytes, sel_bytes)));
+    SQGR_HIP(hipcub::DeviceRadixSort::SortKeys(tmp.p, sort_bytes, keys, sorted, (int)m, 0, 56, st));
+    k_seg_classify<<<(unsigned)ceil_div(m, 256), 256, 0, st>>>(sorted, m, seg_item, res_item, seg_flag, res_flag);
+    SQGR_HIP(hipGetLastError());
+    // stable compactions: the entries keep the order (r0, d) of the sorted keys; `keys` is free again and takes the residual edges
+    SQGR_HIP(hipcub::DeviceSelect::Flagged(tmp.p, sel_bytes, seg_item, seg_flag, seg_out, counts, (int)m, st));
+    SQGR_HIP(hipcub::DeviceSelect::Flagged(tmp.p, sel_bytes, res_item, res_flag, keys, counts + 1, (int)m, st));
+    int h_counts[2] = {0, 0};
+    SQGR_HIP(hipMemcpyAsync(h_counts, counts, 8, hipMemcpyDeviceToHost, st));
+    SQGR_HIP(hipStreamSynchronize(st));
+    const int64_t ns = h_counts[0], nr = h_counts[1];
+    const int64_t padded = ceil_div(ns, SEG_ITER) * SEG_ITER + SEG_PAD;
+    SQGR_TRY(seg.alloc((size_t)padded * 2));
+    SQGR_TRY(seg_res.alloc((size_t)nr + LIST_PAD));
+    k_seg_pack<<<(unsigned)ceil_div(padded / 4, 256), 256, 0, st>>>(seg_out, (uint32_t)ns, (uint32_t)(padded / 4), seg.p);
+    SQGR_HIP(hipGetLastError());
+    if (nr) SQGR_HIP(hipMemcpyAsync(seg_res.p, keys, (size_t)nr * sizeof(int2), hipMemcpyDeviceToDevice, st));
+    SQGR_HIP(hipMemsetAsync(seg_res.p + nr, 0, (size_t)LIST_PAD * sizeof(int2), st));
+    SQGR_HIP(hipStreamSynchronize(st));
+    if (n_half - nr != n_seg_edges) {
+        set_error("internal error: the segment list covers %lld half edges, the count on the CSR said %lld", (long long)(n_half - nr), (long long)n_seg_edges);
+        return SQGR_ERR_HIP;
+    }
+    n_seg = ns;
+    n_seg_padded = padded;
+    n_seg_res = nr;
     return SQGR_OK;
 }
 
@@ -1107,6 +1294,42 @@ int sqgr_spatial_order(sqgr_ctx* ctx, const double* xy, int64_t n, int32_t* out_
     SQGR_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, keys.p, keys_out.p, idx.p, idx_out.p, (int)n, 0, 32, st));
     SQGR_HIP(hipMemcpyAsync(out_order, idx_out.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     SQGR_HIP(hipStreamSynchronize(st));
+    return SQGR_OK;
+}
+
+int sqgr_graph_segments(const sqgr_graph* g, int64_t* out_info, int32_t* out_seg, int32_t* out_res) {
+    SQGR_REQUIRE(g && out_info, "graph/out_info is NULL");
+    SQGR_TRY(g->ensure_seg());
+    const bool built = g->seg_state == 1;
+    out_info[0] = built ? 1 : 0;
+    out_info[1] = built ? g->n_seg : 0;
+    out_info[2] = built ? g->n_seg_padded : 0;
+    out_info[3] = built ? g->n_seg_res : 0;
+    out_info[4] = g->sym_state == 1 ? g->n_half : 0;
+    if (!built) {
+        set_error("no segment list: %s", g->seg_why ? g->seg_why : "not applicable");
+        return SQGR_OK;
+    }
+    SQGR_HIP(hipSetDevice(g->ctx->device));
+    if (out_seg) {  // the groups of four entries, unpacked
+        std::vector<uint32_t> w((size_t)g->n_seg_padded * 2);
+        SQGR_HIP(hipMemcpy(w.data(), g->seg.p, w.size() * 4, hipMemcpyDeviceToHost));
+        for (int64_t e = 0; e < g->n_seg_padded; ++e) {
+            const uint32_t* grp = w.data() + (e >> 2) * 8;
+            const int u = (int)(e & 3), sh = 16 * (u & 1);
+            out_seg[3 * e] = (int32_t)(grp[u] >> 4);
+            out_seg[3 * e + 1] = (int32_t)((grp[4 + (u >> 1)] >> sh) & 0xffffu);
+            out_seg[3 * e + 2] = (int32_t)((grp[6 + (u >> 1)] >> sh) & 0xffffu);
+        }
+    }
+    if (out_res && g->n_seg_res) {
+        std::vector<int2> w((size_t)g->n_seg_res);
+        SQGR_HIP(hipMemcpy(w.data(), g->seg_res.p, w.size() * sizeof(int2), hipMemcpyDeviceToHost));
+        for (int64_t e = 0; e < g->n_seg_res; ++e) {
+            out_res[2 * e] = (int32_t)((uint32_t)w[e].x >> 4);
+            out_res[2 * e + 1] = (int32_t)((uint32_t)w[e].y >> 4);
+        }
+    }
     return SQGR_OK;
 }
 

@@ -16,6 +16,9 @@
 //               permutations; K*K*B counters live in LDS, laid out [pair][b] so that the 32 lanes of a
 //               DS lane group hit distinct banks (B=32) — ds_add_u32 without bank conflicts; block-local
 //               histograms are written out as partials (plain coalesced stores, no global atomics).
+//   k_count_seg : k_count behind another front end for lattice graphs in scan order (K <= 50): the half list as segments of 16
+//               consecutive rows with one column offset (sqgr_graph::ensure_seg) — coalesced row loads instead of gathers
+//               (count_batches selects; SQGR_COUNT_SEGMENTS=0|1|2).
 //   k_reduce  : thread per (pair, b): sums the partials over blocks -> exact per-permutation count,
 //               accumulates d=count-shift and d*d in 64-bit integers (order independent, deterministic).
 // Variants measured on MI355X and dropped (round 3, commit 652982d holds their code; profiles/r03_nhood_experiments.json):
@@ -726,12 +729,23 @@ __device__ __forceinline__ uint32_t pair_index(uint32_t la, uint32_t lb, uint32_
 // term rides in the multiplier of the dot product: v_mad_u32_u16 forms {hi: bytes per cell, lo: (hi + 1) * bytes per cell / 2}
 // and v_dot2_u32_u16 multiplies it with {hi: lo, lo: hi} — five instructions per counter address instead of two.
 // The block's partial is then the LDS image itself (16-bit counters, no h + h^T pass): k_reduce16 expands it.
+// SQGR_COUNT_DOT2=0 (the three-instruction address path) and SQGR_COUNT_DEBUG=<mask> (probe variants of k_count): read once per
+// process, here, for every place that selects a count kernel
+static bool count_dot2() {
+    static const bool on = [] { const char* e = getenv("SQGR_COUNT_DOT2"); return !(e && atoi(e) == 0); }();
+    return on;
+}
+static int count_debug() {
+    static const int v = [] { const char* e = getenv("SQGR_COUNT_DEBUG"); return e ? atoi(e) : 0; }();
+    return v;
+}
+
 template <int B, int MIN_WAVES, bool SELF, bool DOT2 = false, int DBG = 0, int CM = 0>  // DBG (developer probes, bit mask): 1 no atomics, 2 no row gathers, 4 no list loads
 __global__ __launch_bounds__(COUNT_THREADS, MIN_WAVES) void k_count(uint32_t nnz, const int2* __restrict__ coo,
                                                                     const uint8_t* __restrict__ slab_all, int64_t n, int K,
                                                                     int hist_words, uint32_t edges_per_block,
                                                                     uint32_t self_begin, int add_transposed,
-                                                                    uint32_t* __restrict__ partial_all) {
+                                                                    uint32_t* __restrict__ partial_all, int part_first = 0) {
     extern __shared__ uint32_t hist[];
     // this kernel is bound by LDS-atomic and VALU issue; when the VALU-bound shuffle kernel of the next launch group
     // shares the CU (SQGR_NHOOD_STREAMS=2), issue priority keeps the LDS pipe fed
@@ -990,7 +1004,8 @@ __global__ __launch_bounds__(COUNT_THREADS, MIN_WAVES) void k_count(uint32_t nnz
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #endif
     __syncthreads();
-    uint32_t* dst = partial_all + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * hist_words;
+    // part_first > 0: the residual launch behind k_count_seg — a batch's partials are [part_first segment blocks | these blocks]
+    uint32_t* dst = partial_all + ((size_t)blockIdx.y * (gridDim.x + part_first) + part_first + blockIdx.x) * hist_words;
     if constexpr (CM != 0) {  // the partial is the LDS image: 16-bit counters [cell][16], expanded (and h + h^T resolved) by k_reduce16
         for (int i = tid; i < hist_words; i += COUNT_THREADS) dst[i] = hist[i];
         return;
@@ -1003,6 +1018,122 @@ __global__ __launch_bounds__(COUNT_THREADS, MIN_WAVES) void k_count(uint32_t nnz
         }
     } else {
         for (int i = tid; i < hist_words; i += COUNT_THREADS) dst[i] = hist[i];
+    }
+}
+
+// k_count<16, MIN_WAVES, false, true> with another front end: the SEGMENT list of a lattice graph (sqgr_graph::ensure_seg) instead of
+// the half list.  An entry (r0, d, mask) stands for the up to 16 half edges (r0 + j, r0 + j + d), so the sixteen `a` rows are 256
+// contiguous slab bytes and the sixteen `b` rows are 256 contiguous bytes 16 d further: lane l of a wave (edge j = l >> 2, word l & 3
+// of the row, as in k_count) loads slab + 16 r0 + 4 l and that + 16 d — two fully coalesced dword loads per entry, 4 L1 accesses
+// instead of the ~9 a 16-row gather is scattered over — and its increment is bit j of the mask (absent edges add 0, so do the
+// zero-mask entries that pad the list: no tail code).  A wave takes a GROUP of four entries per iteration (U = 4: 16 ds_add_u32 per
+// lane, a block of 16 waves 64 entries = 1024 edge slots, as k_count).  The group's 8 words are fetched by ONE vector load, lane l
+// word l & 7 (one register per stage in flight), and handed to the scalar unit with v_readlane: row offsets and 16 d are formed
+// there, the masks wait for their histogram stage in SGPRs.  No scalar loads: they share lgkmcnt with the LDS atomics.
+// Everything behind the front end is k_count's: per-lane v_perm_b32 selector and v_dot2_u32_u16 address, quad-staggered bank
+// offsets, four back-to-back inline-asm atomics, the three-stage pipeline without prologue code (group words two stages ahead,
+// rows one and two), the explicit wait in front of the flush barrier, the h + h^T flush.  A batch's partials are
+// [part_blocks][K*K*16]: gridDim.x segment blocks, then the blocks of the residual launch (k_count with part_first = gridDim.x).
+template <int MIN_WAVES>
+__global__ __launch_bounds__(COUNT_THREADS, MIN_WAVES) void k_count_seg(uint32_t nseg, const uint32_t* __restrict__ seg,
+                                                                        const uint8_t* __restrict__ slab_all, int64_t n, int K,
+                                                                        int hist_words, uint32_t entries_per_block, int part_blocks,
+                                                                        uint32_t* __restrict__ partial_all) {
+    extern __shared__ uint32_t hist[];
+    __builtin_amdgcn_s_setprio(3);
+    const int tid = threadIdx.x;
+    for (int i = tid; i < hist_words; i += COUNT_THREADS) hist[i] = 0;
+    __syncthreads();
+
+    // (the rows of absent edges, r0 + j (+ d) of a zero bit, reach up to 15 rows past the last spot: their increment is 0 and their
+    // bytes are labels < K all the same — the next batch's rows, or the zero bytes the host keeps behind the launch's last batch)
+    const uint8_t* slab = slab_all + (size_t)blockIdx.y * n * 16;
+    const uint32_t chunk = (uint32_t)xcd_chunk(blockIdx.x, gridDim.x);
+    const uint32_t e0 = chunk * entries_per_block;
+    const uint32_t e1 = min(nseg, e0 + entries_per_block);
+    const uint32_t q = tid & 3, el = tid >> 2, lane = tid & 63, wave = tid >> 6;
+    const uint32_t lane4 = lane * 4;                       // the lane's dword inside the 256 bytes of an entry's rows
+    const uint32_t bit[2] = {lane >> 2, (lane >> 2) + 16};  // its edge's bit in a mask word (even | odd entry of the pair)
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)hist;
+    uint32_t bank_ofs[4], sel[4];  // as k_count (DOT2, 32-bit counters)
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        bank_ofs[s] = (q * 4 + ((s + el) & 3)) * 4 + lds_base;
+        sel[s] = 0x0c000c00u | ((4u + ((s + el) & 3u)) << 16) | ((s + el) & 3u);
+    }
+    const uint32_t dot_k = ((uint32_t)K << 22) | 64u;  // {hi: K << 6, lo: 64}
+    constexpr int U = 4;
+    constexpr uint32_t STEPW = SEG_ITER / 4 * 8;  // words of the groups a block takes per iteration
+
+    auto load_rows = [&](uint32_t v, uint32_t (&ra)[U], uint32_t (&rb)[U], uint32_t (&mk)[2]) {
+        const uint32_t dd[2] = {(uint32_t)__builtin_amdgcn_readlane((int)v, 4), (uint32_t)__builtin_amdgcn_readlane((int)v, 5)};
+        mk[0] = (uint32_t)__builtin_amdgcn_readlane((int)v, 6);
+        mk[1] = (uint32_t)__builtin_amdgcn_readlane((int)v, 7);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t w0 = (uint32_t)__builtin_amdgcn_readlane((int)v, u);
+            const uint32_t d16 = ((u & 1) ? dd[u >> 1] >> 16 : dd[u >> 1] & 0xffffu) << 4;
+            // (buffer loads with these offsets as scalar offsets need no address VALU at all — 44 instead of 52 VALU instructions per
+            // iteration — and measured 3 % SLOWER, 0.963 against 0.935 ms per 2560 permutations: the front end's VALU is not the limiter)
+            const uint32_t oa = w0 + lane4;
+            ra[u] = *reinterpret_cast<const uint32_t*>(slab + oa);
+            rb[u] = *reinterpret_cast<const uint32_t*>(slab + (oa + d16));
+        }
+    };
+    auto histogram = [&](const uint32_t (&row_a)[U], const uint32_t (&row_b)[U], const uint32_t (&mk)[2]) {
+        typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t inc = __builtin_amdgcn_ubfe(mk[u >> 1], bit[u & 1], 1u);
+            uint32_t addr[4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const uint32_t t = __builtin_amdgcn_perm(row_a[u], row_b[u], sel[s]);  // la << 16 | lb
+                addr[s] = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, t), __builtin_bit_cast(u16x2, dot_k), bank_ofs[s], false);
+            }
+            asm volatile("ds_add_u32 %0, %4\n\tds_add_u32 %1, %4\n\tds_add_u32 %2, %4\n\tds_add_u32 %3, %4"
+                         :
+                         : "v"(addr[0]), "v"(addr[1]), "v"(addr[2]), "v"(addr[3]), "v"(inc)
+                         : "memory");
+        }
+    };
+    if (e0 < nseg) {  // (chunks past the end of a short list stay empty; their look-ahead would leave the padding)
+        const uint32_t T = (e1 - e0 + SEG_ITER - 1) / SEG_ITER;
+        const uint32_t* my = seg + ((size_t)(e0 >> 2) + wave) * 8 + (lane & 7);
+        uint32_t ra[3][U], rb[3][U], mk[3][2], ent[3];
+        // k_count's uniform loop: T + 2 stages, the first two histogram nothing, and two dummy row loads in front of it put the loads
+        // in flight that a steady-state stage sees (one wait pattern for every stage)
+        auto dummy_rows = [&](uint32_t (&a)[U], uint32_t (&b)[U]) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                uint32_t ofs = lane4;
+                asm volatile("" : "+v"(ofs));  // (opaque: eight loads, not one)
+                a[u] = *reinterpret_cast<const uint32_t*>(slab + ofs);
+                b[u] = *reinterpret_cast<const uint32_t*>(slab + ofs);
+            }
+        };
+        ent[0] = my[0];
+        dummy_rows(ra[1], rb[1]);
+        ent[1] = my[STEPW];
+        dummy_rows(ra[2], rb[2]);
+        mk[1][0] = mk[1][1] = mk[2][0] = mk[2][1] = 0;
+        for (uint32_t j = 0; j < T + 2; j += 3) {
+#pragma unroll
+            for (int st = 0; st < 3; ++st) {  // stage t = j + st: buffers t % 3 = st
+                ent[(st + 2) % 3] = my[(st + 2) * STEPW];                  // group words of iteration t + 2
+                load_rows(ent[st], ra[st], rb[st], mk[st]);                  // rows of iteration t
+                if (j + st >= 2 && j + st - 2 < T) histogram(ra[(st + 1) % 3], rb[(st + 1) % 3], mk[(st + 1) % 3]);  // iteration t - 2
+            }
+            my += 3 * STEPW;
+        }
+    }
+    // the ds_add_u32 are inline asm, invisible to the compiler's wait counts: see k_count
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __syncthreads();
+    uint32_t* dst = partial_all + ((size_t)blockIdx.y * part_blocks + blockIdx.x) * hist_words;
+    for (int i = tid; i < hist_words; i += COUNT_THREADS) {  // the block's contribution to count = h + h^T, out of LDS
+        const int pair = i >> 4, la = pair / K, lb = pair - la * K;
+        dst[i] = hist[i] + hist[((lb * K + la) << 4) + (i & 15)];
     }
 }
 
@@ -1697,7 +1828,10 @@ struct sqgr_nhood {
     bool tab_lds = true;                   // the label-boundary table fits LDS next to the block table (nhood_build)
     DevBuf<int32_t> spot_of;               // sqgr_nhood_set_spot_map: slab row i holds the labels of the caller's observation spot_of[i]
     bool mapped() const { return spot_of.p != nullptr; }
-    size_t slab_stride() const { return (size_t)nbatch * n * B * (wide() ? 2 : 1); }  // bytes
+    // bytes of one of the two slab buffers: nbatch batches of rows + SEG_SLAB_PAD zero bytes (k_count_seg loads up to 15 rows past a
+    // batch's last spot: rows of absent edges, increment 0 — but their label bytes still form the address of the atomic, so they
+    // have to BE labels: the next batch's rows, or zeros behind the last batch of the launch, see count_batches)
+    size_t slab_stride() const { return (size_t)nbatch * n * B * (wide() ? 2 : 1) + SEG_SLAB_PAD; }
     DevBuf<uint32_t> partial;
     DevBuf<int64_t> acc_sum;
     DevBuf<uint64_t> acc_sq;
@@ -1778,7 +1912,7 @@ struct sqgr_nhood {
     // per batch), fewer ramps and tails (tools/nhood_k_sweep.py --sweep, round 5, permutations/s at 1e6 spots; blocks per batch 8 /
     // 16 / 32 / 64: K = 30 953 k / 948 k / 921 k / 864 k — round 4's 32 was 6 % behind —, K = 64 687 k / 657 k / 602 k / 499 k,
     // K = 100 605 k / 552 k / 450 k / 330 k, K = 200 230 k / 199 k / 149 k / 102 k).  16-bit counters: at least list / chunk_cap().
-    int blocks_for(int nb, bool relaxed = false) const {
+    int blocks_base(int nb, bool relaxed = false) const {
         int want = nblk;
         if (want <= 0) {
             const int cus = ctx->cu_count > 0 ? ctx->cu_count : 256;
@@ -1790,6 +1924,21 @@ struct sqgr_nhood {
             if (need > want) want = (int)(nblk > 0 ? need : ceil_div(need, 8) * 8);
         }
         return want;
+    }
+    // The segment path (k_count_seg over sqgr_graph::seg, then k_count over the residual edges): taken iff the plan would otherwise
+    // run k_count<16, ., false, true> with 32-bit counters on a half list without self loops and the segments cover at least 90 % of
+    // the half edges.  SQGR_COUNT_SEGMENTS (read at every call by resolve_tuning): 0 never, 2 required — whatever the coverage, and
+    // a plan that is not eligible is an error that names the reason —, unset | 1: automatic.
+    bool seg_active = false;
+    // blocks of the residual launch behind `nseg_blk` segment blocks: about as many edges per block as a segment block stands for
+    int seg_res_blocks(int nseg_blk) const {
+        if (!seg_active || g->n_seg_res == 0) return 0;
+        const int64_t per = std::max<int64_t>(ceil_div(std::max<int64_t>(g->n_seg_edges, 1), nseg_blk), 1024);
+        return (int)std::min<int64_t>(nseg_blk, ceil_div(g->n_seg_res, per));
+    }
+    int blocks_for(int nb, bool relaxed = false) const {
+        const int base = blocks_base(nb, relaxed);
+        return base + seg_res_blocks(base);
     }
     int nblk_launch = 0;  // blocks per batch of the launch in flight (count -> reduce)
     int sym_launch = 0;   // k_reduce mode of the launch in flight (0 full edge list, 1 half list, 2 half list with self loops)
@@ -1828,6 +1977,37 @@ int sqgr_nhood::resolve_tuning() {
             nbatch = (int)std::max<int64_t>(1, std::min<int64_t>(160, fit));
         }
     }
+    seg_active = false;
+    const char* env_seg = getenv("SQGR_COUNT_SEGMENTS");
+    const int seg_mode = env_seg ? atoi(env_seg) : 1;
+    if (g && seg_mode != 0) {
+        const char* why = nullptr;
+        if (wide() || B != 16) why = "32-wide label rows or more than 256 clusters";
+        else if (be() != 16 || cm()) why = "the counters of 16 permutations do not fit LDS in 32 bits (more than 50 clusters)";
+        else if (!count_dot2() || count_debug() != 0) why = "SQGR_COUNT_DOT2=0 or a probe variant is selected";
+        else {
+            // automatic: the coverage is counted on the CSR first (one pass, no sort, 8 bytes of workspace), so that a graph without
+            // segments — kNN, Delaunay, a Z-order twin — never pays for the list; required: the list whatever it covers
+            int rc = g->seg_coverage();
+            if (rc == SQGR_OK && g->seg_state == 0 && (seg_mode == 2 || g->n_seg_edges * 10 >= g->n_half * 9)) rc = g->ensure_seg();
+            if (rc != SQGR_OK) {  // the list is an optimisation: without it (out of memory, most likely) the plan runs as it always did
+                if (seg_mode == 2) return rc;
+                (void)hipGetLastError();
+                why = "the segment list could not be built";
+            } else if (g->seg_state == -1) {
+                why = g->seg_why ? g->seg_why : "the graph has no segment list";
+            } else if (seg_mode != 2 && g->n_seg_edges * 10 < g->n_half * 9) {
+                why = "the segments cover less than 90 % of the half edges";
+            } else if (g->seg_state != 1) {
+                why = "the segment list could not be built";
+            }
+        }
+        if (seg_mode == 2 && why) {
+            set_error("SQGR_COUNT_SEGMENTS=2: the segment kernel does not take this plan: %s", why);
+            return SQGR_ERR_UNSUPPORTED;
+        }
+        seg_active = !why;
+    }
     return SQGR_OK;
 }
 
@@ -1835,7 +2015,13 @@ int sqgr_nhood::ensure_workspace(bool need_perms) {
     SQGR_TRY(resolve_tuning());
     const size_t hw = (size_t)hist_words();
     SQGR_TRY(keys.ensure(2 * keys_stride()));
-    SQGR_TRY(slab.ensure(2 * slab_stride()));
+    {   // the zero bytes behind the rows of either buffer (slab_stride) are written here, once per allocation, and never again
+        const uint8_t* had = slab.p;
+        const size_t had_n = slab.n;
+        SQGR_TRY(slab.ensure(2 * slab_stride()));
+        if (slab.p != had || slab.n != had_n)
+            for (int i = 1; i <= 2; ++i) SQGR_HIP(hipMemsetAsync(slab.p + i * slab_stride() - SEG_SLAB_PAD, 0, SEG_SLAB_PAD, ctx->stream));
+    }
     for (int i = 0; i < 2; ++i) {
         if (!ev_shuffled[i]) SQGR_HIP(hipEventCreateWithFlags(&ev_shuffled[i], hipEventDisableTiming));
         if (!ev_counted[i]) SQGR_HIP(hipEventCreateWithFlags(&ev_counted[i], hipEventDisableTiming));
@@ -1862,6 +2048,37 @@ int sqgr_nhood::count_batches(int nb, int buf) {
     const int ncell = cells();
     if (nnz == 0) {  // no edges: every count is zero
         SQGR_HIP(hipMemsetAsync(partial.p, 0, (size_t)nb * nblk_launch * part_words() * 4, st));
+        return SQGR_OK;
+    }
+    if (seg_active) {
+        const int nseg_blk = blocks_base(nb, columns_valid), nres_blk = seg_res_blocks(nseg_blk);
+        nblk_launch = nseg_blk + nres_blk;
+        const size_t lds = (size_t)hw * 4;
+        const uint32_t nseg = (uint32_t)g->n_seg, nres = (uint32_t)g->n_seg_res;
+        const uint32_t epb = (uint32_t)(ceil_div(ceil_div(std::max<int64_t>(nseg, 1), nseg_blk), SEG_ITER) * SEG_ITER);  // whole iterations
+        LaunchTimer t(ctx, "nhood_count_seg_half");  // one bracket around both launches: per launch GROUP, like every nhood_count* timer
+        // a short launch (the last group of a run, injected label vectors): behind its last batch lie the rows of a batch this launch
+        // did not fill — stale or never written; the bytes the kernel can reach there are zeroed (a full launch ends at the buffer's own
+        // zero bytes), so that no label byte >= K ever forms the address of an LDS atomic
+        if (nb < nbatch) SQGR_HIP(hipMemsetAsync(const_cast<uint8_t*>(slab_p) + (size_t)nb * n * 16, 0, SEG_SLAB_PAD, st));
+        if (lds * 2 <= LDS_BUDGET) {
+            SQGR_TRY(allow_lds(k_count_seg<8>, lds));
+            k_count_seg<8><<<dim3(nseg_blk, nb), COUNT_THREADS, lds, st>>>(nseg, g->seg.p, slab_p, n, K, hw, epb, nblk_launch, partial.p);
+        } else {
+            SQGR_TRY(allow_lds(k_count_seg<4>, lds));
+            k_count_seg<4><<<dim3(nseg_blk, nb), COUNT_THREADS, lds, st>>>(nseg, g->seg.p, slab_p, n, K, hw, epb, nblk_launch, partial.p);
+        }
+        if (nres_blk) {  // the half edges outside the segments: k_count as on the half list, partial slots behind the segment blocks'
+            const uint32_t epb_r = (uint32_t)(ceil_div(ceil_div((int64_t)nres, nres_blk), 1024) * 1024);
+            if (lds * 2 <= LDS_BUDGET) {
+                SQGR_TRY(allow_lds((k_count<16, 8, false, true>), lds));
+                k_count<16, 8, false, true><<<dim3(nres_blk, nb), COUNT_THREADS, lds, st>>>(nres, g->seg_res.p, slab_p, n, K, hw, epb_r, nres, 1, partial.p, nseg_blk);
+            } else {
+                SQGR_TRY(allow_lds((k_count<16, 4, false, true>), lds));
+                k_count<16, 4, false, true><<<dim3(nres_blk, nb), COUNT_THREADS, lds, st>>>(nres, g->seg_res.p, slab_p, n, K, hw, epb_r, nres, 1, partial.p, nseg_blk);
+            }
+        }
+        SQGR_HIP(hipGetLastError());
         return SQGR_OK;
     }
     if (wide()) {
@@ -1985,7 +2202,7 @@ int sqgr_nhood::count_batches(int nb, int buf) {
     k_count<BB, MW, SELF><<<grid, COUNT_THREADS, lds, st>>>(m, list, slab_p, n, K, hw, epb, self_begin, addt, partial.p)
 #define SQGR_COUNT_D(BB, MW, SELF) \
     k_count<BB, MW, SELF, true><<<grid, COUNT_THREADS, lds, st>>>(m, list, slab_p, n, K, hw, epb, self_begin, addt, partial.p)
-        static const bool dot2 = [] { const char* e = getenv("SQGR_COUNT_DOT2"); return !(e && atoi(e) == 0); }();
+        const bool dot2 = count_dot2();
         if (B == 32) {
             LaunchTimer t(ctx, half ? "nhood_count_b32_half" : "nhood_count_b32");
             if (self) {
@@ -1997,7 +2214,7 @@ int sqgr_nhood::count_batches(int nb, int buf) {
             }
         } else {
             LaunchTimer t(ctx, half ? "nhood_count_b16_half" : (split_list ? "nhood_count_b16_split" : "nhood_count_b16"));
-            static const int dbg = [] { const char* e = getenv("SQGR_COUNT_DEBUG"); return e ? atoi(e) : 0; }();
+            const int dbg = count_debug();
             if (dot2 && dbg && lds * 2 <= LDS_BUDGET && !self) {
 #define SQGR_COUNT_DBG(D) \
     case D: k_count<16, 8, false, true, D><<<grid, COUNT_THREADS, lds, st>>>(m, list, slab_p, n, K, hw, epb, self_begin, addt, partial.p); break
