@@ -87,7 +87,7 @@ def test_counts_device_generator_match_oracle(L, ctx):
 
 
 def test_more_than_256_clusters_in_tiles(L, ctx):
-    """256 < K <= 2048: 16-bit labels from both generators, group sums in cluster tiles of <= 255 clusters sharing one
+    """256 < K <= 65535: 16-bit labels from both generators, group sums in cluster tiles of <= 255 clusters sharing one
     permutation, scores straight from global memory.  Counts and group means bit for bit like the small-K path."""
     n, g, k = 1500, 6, 300
     data, cl, inter, cp = _problem(n, g, k, seed=21, density=0.5, n_inter=12)
