@@ -308,15 +308,57 @@ __global__ __launch_bounds__(256) void k_shuffle(int64_t n, const uint32_t* __re
 // (32 bytes per a and group, the packing of the sigma keys) for its row pair before the spot loop; a spot then reads its two rows
 // with two 16-byte LDS loads per group, and round 1 of a pair is add / subtract / min: the stored value is < B, so b + T < 2B <=
 // 2^15 has no 16-bit carry and ONE conditional subtraction reduces it — the same b' as the two subtractions of b + F_B, since
-// (b + F) mod B == (b + (F mod B)) mod B (tests/test_shuffle_table_cpu.py).  10 packed instructions per pair become 3; round 2,
-// the block-table look-up, the sentinel test and the exact route are k_shuffle's (the exact route re-walks sigma with the real
-// keys, which it loads itself: the 16 k0 words are not live in the spot loop).  1024-thread blocks, two per CU (2 x 69 KB of LDS
-// at A = 1024): <= 64 VGPRs.  LDS: [blk_words] block table at byte offset 0, [kpad] boundaries, then T at word tab_word0.
+// (b + F) mod B == (b + (F mod B)) mod B (tests/test_shuffle_table_cpu.py).  10 packed instructions per pair become 3; round 2
+// and the block-table look-up are k_shuffle's.  1024-thread blocks, two per CU (2 x 69 KB of LDS at A = 1024): <= 64 VGPRs.
+// LDS: [blk_words] block table at byte offset 0, [kpad] boundaries, then T at word tab_word0.
+// The spot loop carries nothing a label does not need (same labels, bit for bit — tests/test_shuffle_valu_*.py;
+// profiles/shuffle_valu_before_after.md): C1 sits in a VGPR so that the key is v_pk_mad_u16's one scalar operand; without a spot
+// map the rank's digits advance by the grid stride's instead of being divided out; pi_g's first walk runs unmasked and only an
+// image outside [0, n) enters the masked loop; sigma's high digit is carried as the block table's byte offset (the exact route
+// shifts it back); a word's first label is written with zero padding.  The sentinel test and the exact route are k_shuffle's,
+// per word: one test per 16 labels with an exact route that starts again from the group image was built and measured slower —
+// a WAVE meets a sentinel in 37 % of its groups at 1e6 spots, and every such group then walked all its words.
 constexpr int SHUF_TAB_THREADS = 1024;
 constexpr uint32_t SHUF_TAB_MAX_A = 1024;  // 2 groups x A x 32 bytes = 64 KB: two blocks per CU
 constexpr int SHUF_TAB_BLOCKS_PER_CU = 20;  // grid cap (launch_shuffle_raw)
 constexpr int SHUF_TAB_MIN_TRIPS = 16;      // automatic selection: spots per thread of a resident block (launch_shuffle_raw)
-template <bool SMALLK>
+static_assert(SHUF_TAB_MAX_A * 4u <= (1u << 12), "k_shuffle_tab carries the high digit scaled by 4 in a 16-bit half: ash - 2 >= 4, a << 2 < 2^12");
+
+// feistel_F2 with the multiplier C1 (both halves) in a register the caller keeps opaque to the compiler: v_pk_mad_u16 may name
+// ONE scalar register on gfx9, so with C1 a scalar constant every uniform key word was first copied into a VGPR (one v_mov_b32
+// per evaluation); with C1 in a VGPR the key is the instruction's scalar operand.
+__device__ __forceinline__ u16x2 shuf_tab_F2(u16x2 v, u16x2 k, u16x2 sh, u16x2 c1) {
+    u16x2 x = v * c1 + k;
+    x ^= x >> (u16x2)(7);
+    x *= (u16x2)(FEISTEL_C2);
+    return x >> sh;
+}
+// feistel_rounds<1> on shuf_tab_F2
+__device__ __forceinline__ void shuf_tab_rounds(u16x2& a, u16x2& b, const uint32_t (&kp)[8], u16x2 am, u16x2 ash, u16x2 bsh, u16x2 BB,
+                                                u16x2 c1) {
+#pragma unroll
+    for (int r = 0; r < FEISTEL_ROUNDS; r += 2) {
+        a = (a + shuf_tab_F2(b, __builtin_bit_cast(u16x2, kp[r]), ash, c1)) & am;
+        u16x2 t = b + shuf_tab_F2(a, __builtin_bit_cast(u16x2, kp[r + 1]), bsh, c1);
+        t = __builtin_elementwise_min(t, (u16x2)(t - BB));
+        b = __builtin_elementwise_min(t, (u16x2)(t - BB));
+    }
+}
+// put_label<0, 0> as the FIRST label of a word: the other three bytes are written as zeros (no cleared register to preserve)
+__device__ __forceinline__ uint32_t first_label(uint32_t e, uint32_t bpk, uint32_t zero) {
+    uint32_t word;
+    asm("v_cmp_le_u32_sdwa vcc, %1, %2 src0_sel:WORD_1 src1_sel:WORD_0\n\t"
+        "v_addc_co_u32_sdwa %0, vcc, %1, %3, vcc dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:DWORD\n\t"
+        "s_nop 0"
+        : "=v"(word)
+        : "v"(e), "v"(bpk), "v"(zero)
+        : "vcc");
+    return word;
+}
+
+// NOMAP: no spot map — the rank of slab row i is i itself, and its digits (a0, b0) advance with the grid stride instead of being
+// divided out per spot.
+template <bool SMALLK, bool NOMAP>
 __global__ __launch_bounds__(SHUF_TAB_THREADS, 8) void k_shuffle_tab(int64_t n, const uint32_t* __restrict__ cum, int kpad, int blk_words, int K,
                                                                   const uint32_t* __restrict__ keys, LibDom dom0, int nrows,
                                                                   uint8_t* __restrict__ slab_all, int pw, const int32_t* __restrict__ spot_of,
@@ -359,49 +401,81 @@ __global__ __launch_bounds__(SHUF_TAB_THREADS, 8) void k_shuffle_tab(int64_t n, 
     auto blk_at = [&](uint32_t byte_off) { return *reinterpret_cast<lds_word*>((uintptr_t)byte_off); };
     const uint32_t tabA = (uint32_t)tab_word0 * 4u, tabB = tabA + dom.A * 32u;  // byte offsets (multiples of 32)
     const u16x2 am = (u16x2)((unsigned short)(dom.A - 1u));
-    const u16x2 ash = (u16x2)((unsigned short)dom.ash);
-    for (int64_t i = blockIdx.x * (int64_t)SHUF_TAB_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * SHUF_TAB_THREADS) {
-    const uint32_t x0 = spot_of ? (uint32_t)spot_of[i] : (uint32_t)i;
-    const uint32_t a0 = x0 / dom.B, b0 = x0 - a0 * dom.B;
-    // pi_gA (low halves) and pi_gB (high halves) in one packed evaluation; cycle walk per half (k_shuffle)
+    const u16x2 ash = (u16x2)((unsigned short)dom.ash), bsh = (u16x2)((unsigned short)dom.bsh);
+    // the high digit is carried scaled by 4, the byte offset into the block table:  ((gsa + (x >> ash)) & am) << 2  ==
+    // ((gsa << 2) + (x >> (ash - 2))) & (am << 2)  in every 16-bit half — the two low bits of x >> (ash - 2) never carry into a sum
+    // that is masked above them, and ash >= 6 (A <= 1024) keeps a << 2 < 2^12 (tests/test_shuffle_valu_cpu.py)
+    const u16x2 am4 = (u16x2)((unsigned short)((dom.A - 1u) << 2));
+    const u16x2 ash4 = (u16x2)((unsigned short)(dom.ash - 2u));
+    uint32_t c1w = FEISTEL_C1 * 0x10001u;
+    asm volatile("" : "+v"(c1w));  // opaque: stays a VGPR (shuf_tab_F2)
+    const u16x2 c1 = __builtin_bit_cast(u16x2, c1w);
+    const uint32_t n32 = (uint32_t)n, stride = gridDim.x * (uint32_t)SHUF_TAB_THREADS;  // n <= 2^20
+    uint32_t i = blockIdx.x * (uint32_t)SHUF_TAB_THREADS + threadIdx.x;
+    // NOMAP: ONE division per thread; a trip then adds the stride's digits with one conditional wrap (sa * B + sb == stride)
+    // (the stride's digits are kept in VGPRs: as scalars they stay live through the loop and push key words into spill lanes)
+    uint32_t sa = 0, sb = 0, a0 = 0, b0 = 0;
+    if constexpr (NOMAP) {
+        sa = stride / dom.B;
+        sb = stride - sa * dom.B;
+        asm volatile("" : "+v"(sa), "+v"(sb));
+        a0 = i / dom.B;
+        b0 = i - a0 * dom.B;
+    }
+    uint32_t kp[8];  // pi_g's packed keys, in VGPRs: eight scalars fewer live through the loop
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        kp[r] = (kgA[r] & 0xFFFFu) | (kgB[r] & 0xFFFF0000u);
+        asm volatile("" : "+v"(kp[r]));
+    }
+    for (; i < n32; i += stride) {
+    if constexpr (!NOMAP) {
+        const uint32_t x0 = (uint32_t)spot_of[i];
+        a0 = x0 / dom.B;
+        b0 = x0 - a0 * dom.B;
+    }
+    // pi_gA (low halves) and pi_gB (high halves) in one packed evaluation.  The first walk runs without masks; an image outside
+    // [0, n) (fewer than 1 in B of them) is walked again per half in a cold loop, as in k_shuffle
     u16x2 ga = (u16x2)((unsigned short)a0), gb = (u16x2)((unsigned short)b0);
     {
-        uint32_t kp[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) kp[r] = (kgA[r] & 0xFFFFu) | (kgB[r] & 0xFFFF0000u);
-        const uint32_t* const pg[1] = {kp};
-        bool need0 = true, need1 = true;
-        do {
-            u16x2 na[1] = {ga}, nb[1] = {gb};
-            feistel_rounds<1>(na, nb, dom, pg);
-            if (need0) { ga.x = na[0].x; gb.x = nb[0].x; }
-            if (need1) { ga.y = na[0].y; gb.y = nb[0].y; }
+        shuf_tab_rounds(ga, gb, kp, am, ash, bsh, BB, c1);
+        bool need0 = __umul24((uint32_t)ga.x, dom.B) + (uint32_t)gb.x >= dom.n;
+        bool need1 = __umul24((uint32_t)ga.y, dom.B) + (uint32_t)gb.y >= dom.n;
+        while (__builtin_expect(need0 | need1, 0)) {
+            u16x2 na = ga, nb = gb;
+            shuf_tab_rounds(na, nb, kp, am, ash, bsh, BB, c1);
+            if (need0) { ga.x = na.x; gb.x = nb.x; }
+            if (need1) { ga.y = na.y; gb.y = nb.y; }
             need0 = __umul24((uint32_t)ga.x, dom.B) + (uint32_t)gb.x >= dom.n;
             need1 = __umul24((uint32_t)ga.y, dom.B) + (uint32_t)gb.y >= dom.n;
-        } while (need0 | need1);
+        }
+    }
+    if constexpr (NOMAP) {
+        a0 += sa;
+        b0 += sb;
+        if (b0 >= dom.B) { b0 -= dom.B; ++a0; }
     }
     // the 16 labels of one group: round 1 of sigma_p from the table row of the group image's high digit, round 2 as in k_shuffle
-    auto emit_group = [&](const u16x2 gsa, const u16x2 gsb, const uint32_t row_off, const uint32_t* ks, uint32_t (&out)[4]) {
+    auto emit_group = [&](const uint32_t ga1, const uint32_t gb1, const uint32_t row_off, const uint32_t* ks, uint32_t (&out)[4]) {
+        const u16x2 gsa4 = (u16x2)((unsigned short)(ga1 << 2)), gsb = (u16x2)((unsigned short)gb1);
         const u32x4 r0 = *reinterpret_cast<lds_row*>((uintptr_t)row_off);
         const u32x4 r1 = *reinterpret_cast<lds_row*>((uintptr_t)(row_off + 16u));
         const uint32_t f1[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
 #pragma unroll
         for (int w = 0; w < FEISTEL_GROUP / 4; ++w) {
-            uint32_t word = 0;
-            uint32_t apk[2], bpk[2];  // sigma images of the word's two pairs (kept for the exact route)
+            uint32_t word;
+            uint32_t a4pk[2], bpk[2];  // sigma images of the word's two pairs, the high digits scaled by 4 (kept for the exact route)
 #pragma unroll
             for (int jj = 0; jj < 2; ++jj) {
                 const u16x2 t = gsb + __builtin_bit_cast(u16x2, f1[w * 2 + jj]);
                 const u16x2 b = __builtin_elementwise_min(t, (u16x2)(t - BB));
                 const u16x2 k1 = __builtin_bit_cast(u16x2, ks[(w * 2 + jj) * 2 + 1]);
-                const u16x2 a = (gsa + feistel_F2(b, k1, ash)) & am;
-                apk[jj] = __builtin_bit_cast(uint32_t, a);
                 bpk[jj] = __builtin_bit_cast(uint32_t, b);
-                const uint32_t a4 = apk[jj] << 2;  // both halves at once (a < 2^14): byte offsets into the block table
-                const uint32_t e0 = blk_at(a4 & 0xFFFFu);
-                const uint32_t e1 = blk_at(a4 >> 16);
+                a4pk[jj] = __builtin_bit_cast(uint32_t, (u16x2)((gsa4 + shuf_tab_F2(b, k1, ash4, c1)) & am4));
+                const uint32_t e0 = blk_at(a4pk[jj] & 0xFFFFu);
+                const uint32_t e1 = blk_at(a4pk[jj] >> 16);
                 if (jj == 0) {
-                    put_label<0, 0>(word, e0, bpk[jj], zero);
+                    word = first_label(e0, bpk[jj], zero);
                     put_label<1, 1>(word, e1, bpk[jj], zero);
                 } else {
                     put_label<2, 0>(word, e0, bpk[jj], zero);
@@ -421,7 +495,7 @@ __global__ __launch_bounds__(SHUF_TAB_THREADS, 8) void k_shuffle_tab(int64_t n, 
                     if (K <= 255 && ((word >> (8 * j)) & 0xFFu) < (uint32_t)K) continue;
                     const int jj = j >> 1, sh = (j & 1) * 16;
                     const uint32_t* sk = ks + (w * 2 + jj) * 2;
-                    uint32_t a = (apk[jj] >> sh) & 0xFFFFu, b = (bpk[jj] >> sh) & 0xFFFFu;
+                    uint32_t a = ((a4pk[jj] >> sh) & 0xFFFFu) >> 2, b = (bpk[jj] >> sh) & 0xFFFFu;
                     uint32_t x = a * dom.B + b;
                     if (x >= dom.n) {
                         const uint32_t k0 = (sk[0] >> sh) & 0xFFFFu, k1 = (sk[1] >> sh) & 0xFFFFu;
@@ -446,8 +520,8 @@ __global__ __launch_bounds__(SHUF_TAB_THREADS, 8) void k_shuffle_tab(int64_t n, 
         }
     };
     uint32_t outA[4], outB[4];
-    emit_group((u16x2)(ga.x), (u16x2)(gb.x), tabA + (uint32_t)ga.x * 32u, ksA, outA);
-    if (store1) emit_group((u16x2)(ga.y), (u16x2)(gb.y), tabB + (uint32_t)ga.y * 32u, ksB, outB);
+    emit_group((uint32_t)ga.x, (uint32_t)gb.x, tabA + (uint32_t)ga.x * 32u, ksA, outA);
+    if (store1) emit_group((uint32_t)ga.y, (uint32_t)gb.y, tabB + (uint32_t)ga.y * 32u, ksB, outB);
     slab_store16(slab_all + (size_t)row0 * n * 16, n, i, pw, outA[0], outA[1], outA[2], outA[3]);
     if (store1) slab_store16(slab_all + (size_t)row1 * n * 16, n, i, pw, outB[0], outB[1], outB[2], outB[3]);
     }
@@ -2659,15 +2733,18 @@ static int launch_shuffle_raw(sqgr_nhood* p, int B, int nb, const uint32_t* keys
             const unsigned cap = (unsigned)(tab_per_cu * cus) / gy + 1;
             const unsigned trips = (nblk + cap - 1) / cap;
             const unsigned tx = (nblk + trips - 1) / trips;
+#define SQGR_SHUFFLE_TAB(SK, NOMAP)                                                                                             \
+    do {                                                                                                                       \
+        SQGR_TRY(allow_lds(k_shuffle_tab<SK, NOMAP>, lds_tab));                                                                \
+        k_shuffle_tab<SK, NOMAP><<<dim3(tx, gy), SHUF_TAB_THREADS, lds_tab, st>>>(p->n, p->cum.p, p->kpad, p->blk_bytes, p->K, keys, p->dom0, nb, \
+                                                                                slab, pw, p->spot_of.p, (int)tab_word0);        \
+    } while (0)
             if (p->K <= 126) {
-                SQGR_TRY(allow_lds(k_shuffle_tab<true>, lds_tab));
-                k_shuffle_tab<true><<<dim3(tx, gy), SHUF_TAB_THREADS, lds_tab, st>>>(p->n, p->cum.p, p->kpad, p->blk_bytes, p->K, keys, p->dom0, nb, slab, pw,
-                                                                                   p->spot_of.p, (int)tab_word0);
+                if (p->spot_of.p) SQGR_SHUFFLE_TAB(true, false); else SQGR_SHUFFLE_TAB(true, true);
             } else {
-                SQGR_TRY(allow_lds(k_shuffle_tab<false>, lds_tab));
-                k_shuffle_tab<false><<<dim3(tx, gy), SHUF_TAB_THREADS, lds_tab, st>>>(p->n, p->cum.p, p->kpad, p->blk_bytes, p->K, keys, p->dom0, nb, slab, pw,
-                                                                                    p->spot_of.p, (int)tab_word0);
+                if (p->spot_of.p) SQGR_SHUFFLE_TAB(false, false); else SQGR_SHUFFLE_TAB(false, true);
             }
+#undef SQGR_SHUFFLE_TAB
             SQGR_HIP(hipGetLastError());
             return SQGR_OK;
         }
