@@ -345,6 +345,13 @@ int sqgr_knn_self(sqgr_ctx* ctx, const double* xy, int64_t n, int32_t k, int32_t
  * out_indptr int64[n+1], allocate out_indptr[n] entries, call again (capacity = allocated entries). */
 int sqgr_radius_self(sqgr_ctx* ctx, const double* xy, int64_t n, double radius, int64_t* out_indptr, int32_t* out_idx,
                      double* out_d2, int64_t capacity);
+/* The same two searches on 3-D coordinates, xyz: float64[n][3] row-major (stacked sections, volumetric data): squared
+ * distances (dx*dx + dy*dy) + dz*dz, unfused, in coordinate order — sklearn's for coordinates of width 3.  Contracts,
+ * error codes and messages are those of sqgr_knn_self / sqgr_radius_self; a point set that is flat in one or two axes,
+ * or all at one site, is valid input. */
+int sqgr_knn_self3(sqgr_ctx* ctx, const double* xyz, int64_t n, int32_t k, int32_t* out_idx, double* out_d2);
+int sqgr_radius_self3(sqgr_ctx* ctx, const double* xyz, int64_t n, double radius, int64_t* out_indptr, int32_t* out_idx,
+                      double* out_d2, int64_t capacity);
 
 /* ---- ligand-receptor permutation test -------------------------------------------------------------------------------
  * sqgr_ligrec_counts replaces the numba kernel `_score_permutations` (gr/_ligrec.py:616-673) that `_analysis`

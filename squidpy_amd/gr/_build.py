@@ -5,7 +5,7 @@ Drop-ins for ``squidpy.gr.spatial_neighbors_knn`` / ``_radius`` / ``_grid`` and 
 builders gr/neighbors.py:157-269, 335-419; post-processing gr/neighbors.py:441-476; transforms :479-560).
 
 The k-nearest-neighbour and fixed-radius searches — the part that dominates at 1e6 spots — run in ``libsqgr.so`` on a
-device cell list (``csrc/sqgr_neighbors.hip``); the O(nnz) CSR assembly, ring expansion, percentile / interval pruning
+device cell list (``csrc/sqgr_neighbors.hip`` for ``(n, 2)`` coordinates, ``csrc/sqgr_neighbors3d.hip`` for ``(n, 3)``); the O(nnz) CSR assembly, ring expansion, percentile / interval pruning
 and the optional spectral / cosine transforms stay on the host with scipy, written to give the reference's matrices.
 Delaunay graphs take their triangulation from ``scipy.spatial.Delaunay`` (Qhull) on the host exactly as the reference does
 (gr/neighbors.py:319-331, 395-398) — there is no device kernel behind them; edge lengths, pruning and transforms share
@@ -106,8 +106,8 @@ def _build_one(ctx: Context | None, coords: np.ndarray, spec: _Spec) -> tuple[sp
     arrays (row, col, length, alive) and assembled into CSR once at the end."""
     coords = np.asarray(coords, dtype=np.float64)
     uses_device = spec.kind in ("knn", "radius") or (spec.kind == "grid" and not spec.delaunay)
-    if uses_device and (coords.ndim != 2 or coords.shape[1] != 2):
-        raise NotImplementedError(f"The GPU neighbour search handles 2-D coordinates, found shape `{coords.shape}`.")
+    if uses_device and (coords.ndim != 2 or coords.shape[1] not in (2, 3)):
+        raise NotImplementedError(f"The GPU neighbour search handles 2-D or 3-D coordinates, found shape `{coords.shape}`.")
     n = coords.shape[0]
     if spec.kind == "grid":
         adj, dst = _grid_graph(ctx, coords, spec)
