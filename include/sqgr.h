@@ -398,6 +398,25 @@ int sqgr_sepal_run(sqgr_sepal* h, const sqgr_matrix* m, const int32_t* cols, int
 int sqgr_sepal_trace(sqgr_sepal* h, const sqgr_matrix* m, int32_t col, int32_t n_steps, double dt, double* out_conc, double* out_ent);
 int sqgr_sepal_destroy(sqgr_sepal* h);
 
+/* ---- centrality_scores: the integers behind group closeness, group degree and local clustering -------------------------------
+ * Replaces what `centrality_scores` (gr/_nhood.py:245-345) asks of rustworkx and of its numba kernel.  Both entry points take the
+ * graph `_build_graph` (gr/_nhood.py:432-454) builds on the host — A + A^T, diagonal and stored zeros removed, rows sorted: an
+ * undirected simple graph — and return SQGR_ERR_INVALID (sqgr_last_error names which) for a graph that is not structurally
+ * symmetric, has a self loop, or a row that is not strictly increasing (checked on the device).  All results are exact integers;
+ * the caller forms the floats.
+ * sqgr_graph_triangles: out_two_tri int64[n], two_tri[v] = sum over u in N(v) of |N(v) n N(u)| = twice the triangles through v
+ *   (`_local_clustering`, :457-491: cc[v] = two_tri[v] / (k_v (k_v - 1)) for k_v >= 2).
+ * sqgr_group_bfs: one multi-source BFS per group g = {i : labels[i] == g}, 64 groups per sweep of the graph; labels int32[n] in
+ *   [-1, K), -1 = member of no group (the node stays in the graph).  K >= 1.  With d(g, v) the hop distance from the group's
+ *   nearest member to a node v outside the group:
+ *     out_adjacent[g] = #{v : d = 1}                   (group degree centrality = adjacent / (n - |g|))
+ *     out_dist_sum[g] = sum of d over the reached v    (group closeness centrality = (n - |g|) / dist_sum)
+ *     out_reached[g]  = #{v : d finite}                 each int64[K]; an empty group reaches nothing
+ *     *out_levels     = the largest finite d of the call (0: no group reached anything). */
+int sqgr_graph_triangles(sqgr_ctx* ctx, const sqgr_graph* g, int64_t* out_two_tri);
+int sqgr_group_bfs(sqgr_ctx* ctx, const sqgr_graph* g, const int32_t* labels, int32_t K, int64_t* out_adjacent, int64_t* out_dist_sum,
+                   int64_t* out_reached, int64_t* out_levels);
+
 #ifdef __cplusplus
 }
 #endif

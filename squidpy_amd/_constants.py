@@ -39,6 +39,14 @@ class RipleyStat(ModeEnum):
     L = "L"
 
 
+class Centrality(ModeEnum):
+    """Columns of ``centrality_scores``, in the reference's order (_constants/_constants.py:74-77)."""
+
+    DEGREE = "degree_centrality"
+    CLUSTERING = "average_clustering"
+    CLOSENESS = "closeness_centrality"
+
+
 class CorrAxis(ModeEnum):
     """Axis of the FDR correction in ``ligrec`` (_constants/_constants.py:21-23)."""
 
@@ -96,6 +104,7 @@ class _Uns:
     spatial_neighs = staticmethod(lambda value=None: "spatial_neighbors" if value is None else f"{value}_neighbors")
     nhood_enrichment = staticmethod(lambda cluster: cluster + "_nhood_enrichment")
     interaction_matrix = staticmethod(lambda cluster: cluster + "_interactions")
+    centrality_scores = staticmethod(lambda cluster: cluster + "_centrality_scores")
     co_occurrence = staticmethod(lambda cluster: cluster + "_co_occurrence")
     ripley = staticmethod(lambda cluster, mode: f"{cluster}_ripley_{mode}")
     ligrec = staticmethod(lambda cluster, value=None: f"{cluster}_ligrec" if value is None else value)

@@ -105,6 +105,8 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
         C.c_int,
         [C.c_void_p, c_f32p, c_f32p, c_i32p, C.c_int64, C.c_int32, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_i64p],
     ),
+    "sqgr_graph_triangles": (C.c_int, [C.c_void_p, C.c_void_p, c_i64p]),
+    "sqgr_group_bfs": (C.c_int, [C.c_void_p, C.c_void_p, c_i32p, C.c_int32, c_i64p, c_i64p, c_i64p, c_i64p]),
 }
 
 
@@ -479,6 +481,26 @@ def interaction_matrix(ctx: Context, g: Graph, labels: np.ndarray, n_cls: int, w
         ctx.lib, ctx.lib.sqgr_interaction_matrix(ctx.h, g.h, _ptr(labels, c_i32p), n_cls, int(weights), _ptr(out, c_f64p))
     )
     return out
+
+
+def graph_triangles(ctx: Context, g: Graph) -> np.ndarray:
+    """``two_tri[v] = sum over u in N(v) of |N(v) n N(u)|`` (int64[n]) of an undirected simple graph (``sqgr_graph_triangles``)."""
+    out = np.zeros(g.n, dtype=np.int64)
+    _check(ctx.lib, ctx.lib.sqgr_graph_triangles(ctx.h, g.h, _ptr(out, c_i64p)))
+    return out
+
+
+def group_bfs(ctx: Context, g: Graph, labels: np.ndarray, n_cls: int) -> tuple[np.ndarray, np.ndarray, np.ndarray, int]:
+    """One multi-source BFS per group of an undirected simple graph (``sqgr_group_bfs``); ``labels`` in ``[-1, n_cls)``, -1 = no group.
+    Returns ``(adjacent, dist_sum, reached)`` — int64[n_cls] each — and the largest finite distance of the call."""
+    labels = _as(labels, np.int32)
+    if len(labels) != g.n:
+        raise ValueError(f"Expected {g.n} labels, found {len(labels)}.")
+    adjacent, dist_sum, reached = (np.zeros(n_cls, dtype=np.int64) for _ in range(3))
+    levels = np.zeros(1, dtype=np.int64)
+    _check(ctx.lib, ctx.lib.sqgr_group_bfs(ctx.h, g.h, _ptr(labels, c_i32p), int(n_cls), _ptr(adjacent, c_i64p), _ptr(dist_sum, c_i64p),
+                                           _ptr(reached, c_i64p), _ptr(levels, c_i64p)))
+    return adjacent, dist_sum, reached, int(levels[0])
 
 
 class NhoodPlan:

@@ -1,6 +1,6 @@
-"""``nhood_enrichment`` / ``interaction_matrix`` with the reference's signatures on the MI355X path.
+"""``nhood_enrichment`` / ``interaction_matrix`` / ``centrality_scores`` with the reference's signatures on the MI355X path.
 
-Reference: /root/reference/src/squidpy/gr/_nhood.py:146-242 (nhood_enrichment), :349-429
+Reference: /root/reference/src/squidpy/gr/_nhood.py:146-242 (nhood_enrichment), :245-345 (centrality_scores), :349-429
 (interaction_matrix).  All counting and all label shuffling run in ``libsqgr.so`` (HIP); the host only
 validates, uploads and turns exact integer moments into z-scores."""
 
@@ -8,14 +8,26 @@ from __future__ import annotations
 
 import math
 import warnings
+from collections.abc import Iterable
 from typing import Any, NamedTuple
 
 import numpy as np
 import pandas as pd
 
 from .. import _dist
-from .._constants import Key
-from .._lib import Context, Graph, NhoodPlan, cached_graph, default_context, interaction_matrix as _intmat, nhood_counts, nhood_counts_batch
+from .._constants import Centrality, Key
+from .._lib import (
+    Context,
+    Graph,
+    NhoodPlan,
+    cached_graph,
+    default_context,
+    graph_triangles,
+    group_bfs,
+    interaction_matrix as _intmat,
+    nhood_counts,
+    nhood_counts_batch,
+)
 from .._utils import (
     _assert_categorical_obs,
     _assert_connectivity_key,
@@ -31,7 +43,7 @@ from .._utils import (
     spawn_generators,
 )
 
-__all__ = ["nhood_enrichment", "interaction_matrix", "NhoodEnrichmentResult"]
+__all__ = ["nhood_enrichment", "interaction_matrix", "centrality_scores", "NhoodEnrichmentResult"]
 
 
 class NhoodEnrichmentResult(NamedTuple):
@@ -399,4 +411,133 @@ def interaction_matrix(
     if copy:
         return output
     _save_data(adata, attr="uns", key=Key.uns.interaction_matrix(cluster_key), data=output)
+    return None
+
+
+def parse_centralities(score: str | Centrality | Iterable[str | Centrality] | None) -> list[Centrality]:
+    """The columns ``centrality_scores`` computes: ``None`` is all of them in enum order; a string or an enum member is that one; any
+    other iterable is its items in order (a repeated item counts once).  An unknown name raises the enum's ``ValueError``."""
+    if score is None:
+        return list(Centrality)
+    if isinstance(score, (str, Centrality)):
+        return [Centrality(score)]
+    out: list[Centrality] = []
+    for c in score:
+        c = Centrality(c)
+        if c not in out:
+            out.append(c)
+    return out
+
+
+def centrality_graph(conn: Any) -> Any:
+    """The CSR of the reference's ``_build_graph`` (gr/_nhood.py:441-446): ``A + A.T`` without its diagonal and without stored zeros,
+    rows sorted — undirected, unweighted (only the structure is used), no self loops.  ``conn`` is left as it is."""
+    from scipy.sparse import csr_matrix
+
+    adj = csr_matrix(conn)
+    adj = (adj + adj.T).tocsr()
+    adj.setdiag(0)
+    adj.eliminate_zeros()
+    adj.sort_indices()
+    return adj
+
+
+def centrality_from_counts(
+    centralities: list[Centrality],
+    n: int,
+    codes: np.ndarray,
+    n_cls: int,
+    degree: np.ndarray,
+    two_tri: np.ndarray | None,
+    adjacent: np.ndarray | None,
+    dist_sum: np.ndarray | None,
+) -> dict[str, np.ndarray]:
+    """The float64 columns from the device's exact integers, every float formed here:
+    ``cc = two_tri / (k (k - 1))`` (0 for k < 2) and ``cc[idx].mean()``; ``adjacent / (n - |S|)``; ``(n - |S|) / dist_sum``.
+    An empty group, a group of all nodes and a distance sum of 0 give 0.0."""
+    size = np.bincount(codes[codes >= 0], minlength=n_cls).astype(np.int64)
+    out: dict[str, np.ndarray] = {}
+    for c in centralities:
+        col = np.zeros(n_cls, dtype=np.float64)
+        if c == Centrality.CLUSTERING:
+            k = degree.astype(np.int64)
+            cc = np.zeros(n, dtype=np.float64)
+            ok = k >= 2
+            cc[ok] = two_tri[ok] / (k[ok] * (k[ok] - 1))
+            for g in range(n_cls):
+                idx = np.where(codes == g)[0]
+                col[g] = float(cc[idx].mean()) if 0 < len(idx) < n else 0.0
+        else:
+            for g in range(n_cls):
+                rest = n - int(size[g])
+                if size[g] == 0 or rest == 0:
+                    continue
+                if c == Centrality.DEGREE:
+                    col[g] = int(adjacent[g]) / rest
+                elif int(dist_sum[g]) != 0:
+                    col[g] = rest / int(dist_sum[g])
+        out[c.s] = col
+    return out
+
+
+def centrality_scores(
+    adata: Any,
+    cluster_key: str,
+    score: str | Iterable[str] | None = None,
+    connectivity_key: str | None = None,
+    copy: bool = False,
+    n_jobs: int | None = None,
+    backend: str = "loky",
+    show_progress_bar: bool = False,
+    *,
+    table_key: str | None = None,
+    device: int | None = None,
+) -> pd.DataFrame | None:
+    """Compute centrality scores per cluster (drop-in for ``squidpy.gr.centrality_scores``, gr/_nhood.py:245-345).
+
+    ``score``: ``"closeness_centrality"``, ``"average_clustering"``, ``"degree_centrality"``, an iterable of those, or ``None`` for all
+    three (columns then in the order degree, clustering, closeness).  The graph is the reference's: ``A + A.T`` of the connectivities
+    without diagonal and stored zeros, unweighted; observations with a NaN cluster belong to no group and stay in the graph.
+
+    - ``degree_centrality[g]`` = (nodes outside the group adjacent to a member) / (n - |g|)
+    - ``closeness_centrality[g]`` = (n - |g|) / (sum over the nodes outside the group of their hop distance to the nearest member);
+      an unreachable node adds 0, a sum of 0 scores 0.0
+    - ``average_clustering[g]`` = mean over the members of ``2 T(v) / (k_v (k_v - 1))`` (0 for ``k_v < 2``)
+
+    One level-synchronous sweep of the graph advances the breadth-first searches of up to 64 clusters at once and a per-edge kernel
+    counts the triangles (``csrc/sqgr_centrality.hip``); the device returns exact integers and every float is formed on the host, so
+    closeness and degree equal networkx's ``group_closeness_centrality`` / ``group_degree_centrality`` digit for digit.
+    A category without observations, or one that holds every observation, scores 0.0 in all three columns: rustworkx alone defines
+    what the reference returns there, so these two cases are not pinned to it.
+    ``n_jobs`` is validated, ``backend`` and ``show_progress_bar`` are accepted; they do not influence the GPU path.  Under a process
+    group every rank computes the whole (small) result.
+
+    Returns the float64 frame indexed by the categories if ``copy=True``, else writes it to
+    ``adata.uns['{cluster_key}_centrality_scores']``."""
+    adata = extract_adata_if_sdata(adata, table_key=table_key)
+    connectivity_key = Key.obsp.spatial_conn(connectivity_key)
+    _assert_categorical_obs(adata, cluster_key)
+    _assert_connectivity_key(adata, connectivity_key)
+    centralities = parse_centralities(score)
+    get_n_processes(n_jobs)
+
+    adj = centrality_graph(adata.obsp[connectivity_key])
+    cats = adata.obs[cluster_key].cat.categories
+    codes = adata.obs[cluster_key].cat.codes.to_numpy().astype(np.int32)  # -1 for NaN: no group
+    n, n_cls = adj.shape[0], len(cats)
+
+    two_tri = adjacent = dist_sum = None
+    if n_cls and len(centralities):
+        ctx = default_context(device)
+        graph = cached_graph(ctx, adj, with_data=False)
+        if Centrality.CLUSTERING in centralities:
+            two_tri = graph_triangles(ctx, graph)
+        if Centrality.DEGREE in centralities or Centrality.CLOSENESS in centralities:
+            adjacent, dist_sum, _, _ = group_bfs(ctx, graph, codes, n_cls)
+    cols = centrality_from_counts(centralities, n, codes, n_cls, np.diff(adj.indptr), two_tri, adjacent, dist_sum)
+    df = pd.DataFrame(cols, index=cats, columns=[c.s for c in centralities], dtype=np.float64)
+
+    if copy:
+        return df
+    _save_data(adata, attr="uns", key=Key.uns.centrality_scores(cluster_key), data=df)
     return None
