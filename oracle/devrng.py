@@ -188,7 +188,7 @@ def label_permutations(n: int, seed: int, perms: np.ndarray, lib: int = 0, x: np
 
 def independent_label_permutations(n: int, seed: int, perms: np.ndarray, lib: int = 0) -> np.ndarray:
     """(len(perms), n) label-shuffle permutations of the INDEPENDENT variant of the device generator (SQGR_SHUFFLE_INDEPENDENT=1,
-    sqgr_nhood.hip: k_shuffle_indep): every permutation its own 8-round bijection keyed by ``round_keys(seed, perm, lib)`` — no
+    sqgr_shuffle.hip: k_shuffle_indep): every permutation its own 8-round bijection keyed by ``round_keys(seed, perm, lib)`` — no
     group bijection shared by 16 permutations, no sigma network."""
     return permutation_batch(n, round_keys(seed, np.asarray(perms, dtype=np.int64), lib))
 

@@ -200,6 +200,15 @@ struct DevBuf {
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+constexpr size_t LDS_BUDGET = 160 * 1024;
+// dynamic LDS above 64 KiB must be opted into per kernel
+template <typename KernelT>
+static int allow_lds(KernelT kernel, size_t bytes) {
+    if (bytes > 64 * 1024)
+        SQGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return SQGR_OK;
+}
+
 // zero entries behind the nhood edge lists (sqgr_graph::coo / half): the count kernels' look-ahead loads stay in bounds.  A block's
 // sweep runs ceil((T + 2) / 3) * 3 stages and stage t loads the entries of iteration t + 2: the last load ends at e0 + (T + 6) * STEP
 // with e0 + T * STEP < m + STEP for the tail chunk — SEVEN iterations past the list's end for the widest kernel (one lane per edge,

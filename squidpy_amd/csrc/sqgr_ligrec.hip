@@ -18,7 +18,7 @@
 //                   LDS (row stride 33 doubles: the K rows start in distinct banks), thread = cluster pair, loops
 //                   the permutations of the tile and counts `shuf > obs` in a register; one owner per output cell,
 //                   no atomics.
-// Labels come from the generators of sqgr_nhood.hip (sqgr_shuffle.h): Philox-keyed Feistel (default) or numpy's
+// Labels come from the generators of sqgr_shuffle.hip (sqgr_shuffle.h): Philox-keyed Feistel (default) or numpy's
 // PCG64 streams (bit-for-bit `Generator.shuffle`).
 #include "sqgr_shuffle.h"
 
@@ -157,13 +157,6 @@ __global__ __launch_bounds__(256) void k_ligrec_score_direct(int K, int n_cp, co
     int cnt = 0;
     for (int pl = first_valid; pl < n_valid_perms; ++pl) cnt += (ra[pl] + lb[pl] > o) ? 1 : 0;
     counts[(size_t)i * n_cp + j] += cnt;
-}
-
-template <typename KernelT>
-static int allow_lds(KernelT kernel, size_t bytes) {
-    if (bytes <= 64 * 1024) return SQGR_OK;
-    SQGR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return SQGR_OK;
 }
 
 struct ShufflerGuard {

@@ -255,7 +255,7 @@ def test_permutation_test_moments_and_group_covariance_vs_numpy_streams():
 
 
 def test_independent_label_permutations_are_bijections_of_their_own():
-    """The restatement of the generator's independent variant (sqgr_nhood.hip: k_shuffle_indep): every row a permutation of [0, n),
+    """The restatement of the generator's independent variant (sqgr_shuffle.hip: k_shuffle_indep): every row a permutation of [0, n),
     keyed by the permutation index alone — rows of one 16-group share nothing, and differ from the two-level generator's."""
     n = 1234
     perms = np.arange(16, 48)

@@ -1,4 +1,4 @@
-"""The identity the table variant of the label shuffle rests on (sqgr_nhood.hip: k_shuffle_tab), in numpy on oracle/devrng.py's
+"""The identity the table variant of the label shuffle rests on (sqgr_shuffle.hip: k_shuffle_tab), in numpy on oracle/devrng.py's
 restatement of the generator: sigma's first round `b' = (b + F_B(a, k0)) mod B` may read `F_B(a, k0) mod B` from a table indexed
 by the high digit and reduce the sum with ONE conditional subtraction in 16-bit arithmetic."""
 

@@ -1,4 +1,4 @@
-"""The table variant of the 16-wide label shuffle (sqgr_nhood.hip: k_shuffle_tab — sigma's first round read from an LDS table)
+"""The table variant of the 16-wide label shuffle (sqgr_shuffle.hip: k_shuffle_tab — sigma's first round read from an LDS table)
 against the kernel it replaces and against oracle/devrng.py, bit for bit.  SQGR_SHUFFLE_TABLE, read at every call: 0 never,
 1 whenever the input is eligible, 2 required (an input the table kernel does not take is an error), unset automatic."""
 

@@ -1,4 +1,4 @@
-"""The identities behind the leaner spot loop of the table label shuffle (sqgr_nhood.hip: k_shuffle_tab), in numpy on the
+"""The identities behind the leaner spot loop of the table label shuffle (sqgr_shuffle.hip: k_shuffle_tab), in numpy on the
 arithmetic of oracle/devrng.py's restatement of the generator:
 
 * the high digit of sigma's image may be carried scaled by 4 (the byte offset into the block table) through the second round;

@@ -1,4 +1,4 @@
-"""The leaner spot loop of the table label shuffle (sqgr_nhood.hip: k_shuffle_tab — the rank's digits advanced instead of divided,
+"""The leaner spot loop of the table label shuffle (sqgr_shuffle.hip: k_shuffle_tab — the rank's digits advanced instead of divided,
 an unmasked first walk of the group bijection, the high digit carried as a byte offset that the exact route shifts back, a word's
 first label written with zero padding) against k_shuffle and oracle/devrng.py, bit for bit.  SQGR_SHUFFLE_TABLE: 2 requires the
 table kernel, 0 forbids it, unset selects by launch size.
