@@ -417,6 +417,23 @@ int sqgr_graph_triangles(sqgr_ctx* ctx, const sqgr_graph* g, int64_t* out_two_tr
 int sqgr_group_bfs(sqgr_ctx* ctx, const sqgr_graph* g, const int32_t* labels, int32_t K, int64_t* out_adjacent, int64_t* out_dist_sum,
                    int64_t* out_reached, int64_t* out_levels);
 
+/* ---- calculate_niche_cellcharter: a full-covariance Gaussian mixture fitted by EM in float64 -----------------------------------
+ * Replaces `GaussianMixture(n_components, random_state, init_params="random_from_data").fit(embedding).predict(embedding)`
+ * (gr/_niche.py:1474-1480) and follows scikit-learn 1.7's fit step for step (n_init = 1, covariance_type = "full").
+ * X: n x d row-major float64, finite (the caller checks).  init_rows int64[k]: row init_rows[c] starts as component c with
+ * responsibility 1 — the caller draws `np.random.RandomState(random_state).choice(n, size=k, replace=False)`.
+ * At most max_iter (>= 1) EM steps; a step converges when |lower bound - previous lower bound| < tol and its parameters are kept.
+ * out_weights float64[k], out_means [k x d], out_covariances [k x d x d]: the parameters after the last M-step.
+ * out_lower_bounds float64[max_iter]: one value per step taken, the first *out_n_iter are written; *out_converged 0 | 1.
+ * out_labels int32[n]: argmax over the components of the weighted log-density under the final parameters, first maximum wins.
+ * Two calls with the same arguments return the same bytes: every sum over rows has a fixed order that depends on (n, d, k) alone.
+ * Every device buffer is taken before the first step; a step reads back 16 bytes.  Device memory: (n d + n k) doubles + O(k d^2).
+ * SQGR_ERR_UNSUPPORTED for d > 64, k > 64 or n >= 2^31; SQGR_ERR_INVALID for k > n, an init row outside [0, n), and when a
+ * covariance is not positive definite ("ill-defined empirical covariance": sklearn's ValueError). */
+int sqgr_gmm_fit(sqgr_ctx* ctx, const double* X, int64_t n, int32_t d, int32_t k, const int64_t* init_rows, double reg_covar, double tol,
+                 int32_t max_iter, double* out_weights, double* out_means, double* out_covariances, double* out_lower_bounds,
+                 int32_t* out_n_iter, int32_t* out_converged, int32_t* out_labels);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,11 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     ),
     "sqgr_graph_triangles": (C.c_int, [C.c_void_p, C.c_void_p, c_i64p]),
     "sqgr_group_bfs": (C.c_int, [C.c_void_p, C.c_void_p, c_i32p, C.c_int32, c_i64p, c_i64p, c_i64p, c_i64p]),
+    "sqgr_gmm_fit": (
+        C.c_int,
+        [C.c_void_p, c_f64p, C.c_int64, C.c_int32, C.c_int32, c_i64p, C.c_double, C.c_double, C.c_int32, c_f64p, c_f64p, c_f64p, c_f64p,
+         c_i32p, c_i32p, c_i32p],
+    ),
 }
 
 
@@ -501,6 +506,25 @@ def group_bfs(ctx: Context, g: Graph, labels: np.ndarray, n_cls: int) -> tuple[n
     _check(ctx.lib, ctx.lib.sqgr_group_bfs(ctx.h, g.h, _ptr(labels, c_i32p), int(n_cls), _ptr(adjacent, c_i64p), _ptr(dist_sum, c_i64p),
                                            _ptr(reached, c_i64p), _ptr(levels, c_i64p)))
     return adjacent, dist_sum, reached, int(levels[0])
+
+
+def gmm_fit(
+    ctx: Context, x: np.ndarray, k: int, init_rows: np.ndarray, reg_covar: float, tol: float, max_iter: int
+) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, int, bool, np.ndarray]:
+    """EM of a full-covariance Gaussian mixture on ``x`` (n x d float64, C-contiguous) from the initial centres ``init_rows``
+    (``sqgr_gmm_fit``) -> ``(weights, means, covariances, lower_bounds, n_iter, converged, labels)``."""
+    n, d = x.shape
+    init_rows = _as(init_rows, np.int64)
+    weights = np.zeros(k, dtype=np.float64)
+    means = np.zeros((k, d), dtype=np.float64)
+    cov = np.zeros((k, d, d), dtype=np.float64)
+    lbs = np.zeros(max(int(max_iter), 1), dtype=np.float64)
+    n_iter, conv = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32)
+    labels = np.zeros(n, dtype=np.int32)
+    _check(ctx.lib, ctx.lib.sqgr_gmm_fit(ctx.h, _ptr(x, c_f64p), n, d, int(k), _ptr(init_rows, c_i64p), float(reg_covar), float(tol), int(max_iter),
+                                         _ptr(weights, c_f64p), _ptr(means, c_f64p), _ptr(cov, c_f64p), _ptr(lbs, c_f64p), _ptr(n_iter, c_i32p),
+                                         _ptr(conv, c_i32p), _ptr(labels, c_i32p)))
+    return weights, means, cov, lbs[: int(n_iter[0])].copy(), int(n_iter[0]), bool(conv[0]), labels
 
 
 class NhoodPlan:
