@@ -434,6 +434,50 @@ int sqgr_gmm_fit(sqgr_ctx* ctx, const double* X, int64_t n, int32_t d, int32_t k
                  int32_t max_iter, double* out_weights, double* out_means, double* out_covariances, double* out_lower_bounds,
                  int32_t* out_n_iter, int32_t* out_converged, int32_t* out_labels);
 
+/* ---- niche feature matrices: stage 1 of the three niche flavours, everything in front of scanpy (gr/_niche.py) -------------------
+ * Float64 throughout; every sum over a row's stored entries runs in ascending column order with separately rounded products and
+ * sums (no FMA); two calls with the same arguments return the same bytes.  Graphs must be in canonical CSR form (rows strictly
+ * increasing) where a row is walked as a set (sqgr_shells_create checks on the device).
+ *
+ * sqgr_niche_info: out_info int64[4] = {on-chip capacity of the shell builder: the largest expansion — sum of the lengths of the
+ *   rows of A that a row of hop_{k-1} walks — that stays in LDS, rows above it take the global-memory path; the path count limit
+ *   2^24; columns of X per aggregation block; largest distance}.
+ *
+ * sqgr_shells_create: the hop shells of `_CellcharterEmbedder.get_embedding` (:1336-1355, `_setdiag` / `_hop` :1002-1027) as sorted
+ *   CSR on the device, structure of g only (the caller has checked that every stored value is 1):
+ *     vis_1 = A with its diagonal, every count 1;  hop_1 = A without its diagonal
+ *     P_k = hop_{k-1} @ A (integer path counts, self loops of A take part);  hop_k = P_k > vis_{k-1} (absent = 0);
+ *     vis_k = vis_{k-1} + hop_k                                                for k = 2 .. distance
+ *   Not a BFS: a visited node re-enters shell k whenever more paths reach it than it has been visited.  count_limit: 0, or a lower
+ *   limit than 2^24 (tests); SQGR_ERR_UNSUPPORTED when a path count reaches the limit, and for n >= 2^31 - 1.
+ * sqgr_shells_info: out_info int64[5] = {n, nnz of hop_k, nnz of vis_k, rows of shell k built on the global-memory path, rows whose
+ *   expansion was exactly the on-chip capacity}, 1 <= k <= distance.
+ * sqgr_shells_read: hop_k and vis_k with its visit counts; indptr int64[n + 1], indices / counts int32[nnz]. */
+typedef struct sqgr_shells sqgr_shells;
+int sqgr_niche_info(int64_t* out_info);
+int sqgr_shells_create(sqgr_ctx* ctx, const sqgr_graph* g, int32_t distance, int32_t count_limit, sqgr_shells** out);
+int sqgr_shells_info(const sqgr_shells* h, int32_t k, int64_t* out_info);
+int sqgr_shells_read(const sqgr_shells* h, int32_t k, int64_t* hop_indptr, int32_t* hop_indices, int64_t* vis_indptr, int32_t* vis_indices,
+                     int32_t* vis_counts);
+int sqgr_shells_destroy(sqgr_shells* h);
+/* sqgr_niche_aggregate: out[i * ld_out + j] for every column j of the resident matrix m (dense / CSR / CSC, float32 / float64,
+ *   densified on the device one block of columns at a time), out a HOST array of n rows, ld_out >= n_cols doubles apart.  Exactly
+ *   one of g and shells is given:
+ *     shells, k = 0:      X itself (block 0 of :1345)
+ *     shells, k >= 1:     `_aggregate(adata, _normalize(hop_k), ...)` (:1030-1054): with d = 1 / (stored entries of the row), 1 / 0 -> 0,
+ *                         m1 = sum_j d * x_j; variance != 0: m2 = sum_j d * (x_j * x_j) and m2 - m1 * m1
+ *     g (k, variance 0):  `normalize(A, norm="l1", axis=1) @ X` (:1259-1260): sum_j (a_ij / sum_j |a_ij|) * x_j, a row of norm 0 keeps
+ *                         its entries; a graph created without weights counts 1 per entry. */
+int sqgr_niche_aggregate(sqgr_ctx* ctx, const sqgr_graph* g, const sqgr_shells* shells, int32_t k, const sqgr_matrix* m, int32_t variance,
+                         double* out, int64_t ld_out);
+/* sqgr_niche_label_hops: the hop profiles of `_NhoodProfileEmbedder` (:1117-1209) for hops 1 .. distance in one call:
+ *   out float64[distance][n][K], out[h - 1] = A^h onehot(labels) formed as A (A^(h-1) onehot) — A^h itself is never built.
+ *   labels int32[n], a label outside [0, K) belongs to no category.  weighted != 0: the graph's weights (it must carry them), else 1
+ *   per stored entry.  normalise != 0: every row of every hop is then divided by its sum over the categories (ascending), 0 / 0 -> 0
+ *   (`abs_nhood=False`, :1163-1167). */
+int sqgr_niche_label_hops(sqgr_ctx* ctx, const sqgr_graph* g, const int32_t* labels, int32_t K, int32_t distance, int32_t weighted,
+                          int32_t normalise, double* out);
+
 #ifdef __cplusplus
 }
 #endif

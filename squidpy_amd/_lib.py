@@ -112,6 +112,13 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
         [C.c_void_p, c_f64p, C.c_int64, C.c_int32, C.c_int32, c_i64p, C.c_double, C.c_double, C.c_int32, c_f64p, c_f64p, c_f64p, c_f64p,
          c_i32p, c_i32p, c_i32p],
     ),
+    "sqgr_niche_info": (C.c_int, [c_i64p]),
+    "sqgr_shells_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "sqgr_shells_info": (C.c_int, [C.c_void_p, C.c_int32, c_i64p]),
+    "sqgr_shells_read": (C.c_int, [C.c_void_p, C.c_int32, c_i64p, c_i32p, c_i64p, c_i32p, c_i32p]),
+    "sqgr_shells_destroy": (C.c_int, [C.c_void_p]),
+    "sqgr_niche_aggregate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, c_f64p, C.c_int64]),
+    "sqgr_niche_label_hops": (C.c_int, [C.c_void_p, C.c_void_p, c_i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_f64p]),
 }
 
 
@@ -830,6 +837,74 @@ class DeviceMatrix:
             self.close()
         except Exception:
             pass
+
+
+def niche_info() -> dict[str, int]:
+    """Constants of ``csrc/sqgr_niche.hip`` (``sqgr_niche_info``); needs the library, not a device."""
+    lib = load_library()
+    out = np.zeros(4, dtype=np.int64)
+    _check(lib, lib.sqgr_niche_info(_ptr(out, c_i64p)))
+    return {"shell_capacity": int(out[0]), "count_limit": int(out[1]), "aggregate_columns": int(out[2]), "max_distance": int(out[3])}
+
+
+class HopShells:
+    """The CellCharter hop shells ``hop_k`` / ``vis_k`` of a graph, ``k = 1 .. distance``, resident on the device (``sqgr_shells``)."""
+
+    def __init__(self, ctx: Context, g: Graph, distance: int, count_limit: int = 0):
+        self.ctx, self.n, self.distance = ctx, g.n, int(distance)
+        h = C.c_void_p()
+        _check(ctx.lib, ctx.lib.sqgr_shells_create(ctx.h, g.h, int(distance), int(count_limit), C.byref(h)))
+        self.h = h
+
+    def info(self, k: int) -> dict[str, int]:
+        out = np.zeros(5, dtype=np.int64)
+        _check(self.ctx.lib, self.ctx.lib.sqgr_shells_info(self.h, int(k), _ptr(out, c_i64p)))
+        return {"n": int(out[0]), "hop_nnz": int(out[1]), "vis_nnz": int(out[2]), "spilled_rows": int(out[3]), "rows_at_capacity": int(out[4])}
+
+    def read(self, k: int) -> "tuple[Any, Any]":
+        """``(hop_k, vis_k)`` as scipy CSR matrices: ``hop_k`` of ones (int32), ``vis_k`` of visit counts (int32)."""
+        from scipy import sparse
+
+        info = self.info(k)
+        hp, vp = np.zeros(self.n + 1, dtype=np.int64), np.zeros(self.n + 1, dtype=np.int64)
+        hi, vi, vc = np.zeros(info["hop_nnz"], dtype=np.int32), np.zeros(info["vis_nnz"], dtype=np.int32), np.zeros(info["vis_nnz"], dtype=np.int32)
+        _check(self.ctx.lib, self.ctx.lib.sqgr_shells_read(self.h, int(k), _ptr(hp, c_i64p), _ptr(hi, c_i32p), _ptr(vp, c_i64p), _ptr(vi, c_i32p),
+                                                            _ptr(vc, c_i32p)))
+        hop = sparse.csr_matrix((np.ones(len(hi), dtype=np.int32), hi, hp), shape=(self.n, self.n))
+        vis = sparse.csr_matrix((vc, vi, vp), shape=(self.n, self.n))
+        return hop, vis
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            self.ctx.lib.sqgr_shells_destroy(self.h)
+            self.h = None
+
+    def __del__(self) -> None:  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def niche_aggregate(ctx: Context, m: "DeviceMatrix", out: np.ndarray, *, graph: Graph | None = None, shells: HopShells | None = None, k: int = 0,
+                    variance: bool = False) -> None:
+    """``sqgr_niche_aggregate`` into ``out``: a float64 view of ``m.shape`` whose rows are contiguous (a column range of a wider
+    C-contiguous array)."""
+    if out.dtype != np.float64 or out.shape != tuple(m.shape) or (out.size and (out.strides[1] != 8 or out.strides[0] % 8)):
+        raise ValueError(f"Expected a float64 array of shape {tuple(m.shape)} with contiguous rows.")
+    _check(ctx.lib, ctx.lib.sqgr_niche_aggregate(ctx.h, graph.h if graph is not None else None, shells.h if shells is not None else None, int(k),
+                                                 m.h, int(variance), C.cast(C.c_void_p(out.ctypes.data), c_f64p), max(out.strides[0] // 8, out.shape[1])))
+
+
+def niche_label_hops(ctx: Context, g: Graph, labels: np.ndarray, n_cls: int, distance: int, weighted: bool, normalise: bool) -> np.ndarray:
+    """``out[h - 1] = A^h onehot(labels)`` for ``h = 1 .. distance``, float64 ``(distance, n, n_cls)`` (``sqgr_niche_label_hops``)."""
+    labels = _as(labels, np.int32)
+    if len(labels) != g.n:
+        raise ValueError(f"Expected {g.n} labels, found {len(labels)}.")
+    out = np.zeros((int(distance), g.n, int(n_cls)), dtype=np.float64)
+    _check(ctx.lib, ctx.lib.sqgr_niche_label_hops(ctx.h, g.h, _ptr(labels, c_i32p), int(n_cls), int(distance), int(weighted), int(normalise),
+                                                  _ptr(out, c_f64p)))
+    return out
 
 
 class AutocorrPlan:

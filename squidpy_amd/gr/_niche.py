@@ -3,7 +3,10 @@
 The reference ends in ``sklearn.mixture.GaussianMixture(n_components, random_state, init_params="random_from_data")`` followed by
 ``.fit(embedding).predict(embedding)`` (gr/_niche.py:1474-1480).  ``gmm_fit`` is that fit: the host draws the initial rows from
 numpy's ``RandomState`` exactly as sklearn's ``check_random_state(random_state).choice`` does, everything else runs in
-``csrc/sqgr_gmm.hip`` (``sqgr_gmm_fit``).  Neither this module nor the library imports sklearn."""
+``csrc/sqgr_gmm.hip`` (``sqgr_gmm_fit``).  Neither this module nor the library imports sklearn.
+
+``niche_nhood_profile``, ``niche_utag_features`` and ``niche_cellcharter_features`` are stage 1 of the reference's three niche flavours:
+the feature matrix each of them computes from the spatial graph and hands to scanpy (``csrc/sqgr_niche.hip``)."""
 
 from __future__ import annotations
 
@@ -14,11 +17,12 @@ from typing import Any, NamedTuple
 import numpy as np
 import pandas as pd
 
-from .._lib import SqgrError, default_context
+from .._lib import DeviceMatrix, HopShells, SqgrError, cached_graph, default_context, niche_aggregate, niche_label_hops
 from .._lib import gmm_fit as _gmm_fit
 from .._utils import extract_adata_if_sdata, logg
 
-__all__ = ["calculate_niche_cellcharter", "gmm_fit", "gmm_init_rows", "GMMFit", "GMM_MAX_FEATURES", "GMM_MAX_COMPONENTS"]
+__all__ = ["calculate_niche_cellcharter", "gmm_fit", "gmm_init_rows", "GMMFit", "GMM_MAX_FEATURES", "GMM_MAX_COMPONENTS",
+           "niche_nhood_profile", "niche_utag_features", "niche_cellcharter_features", "hop_shells"]
 
 GMM_MAX_FEATURES = 64    # GMM_MAX of csrc/sqgr_gmm.hip
 GMM_MAX_COMPONENTS = 64
@@ -244,3 +248,258 @@ def calculate_niche_cellcharter(
         result_columns = _cluster(adata.obs, embedding, n_components, random_state, device)
         postprocess_niche_results(adata.obs, result_columns, mask, min_niche_size, None)
     return None if inplace else adata
+
+
+# ---- stage 1 of the three niche flavours: the feature matrix each of them hands to scanpy ----------------------------------------------
+NOT_CATEGORICAL_MSG = "Since adata.obs[groups] does not already have categorical dtype, converting it into categorical type."
+MAX_DISTANCE = 64  # MAX_DISTANCE of csrc/sqgr_niche.hip
+
+
+def _canonical_graph(adata: Any, key: str) -> Any:
+    """``adata.obsp[key]`` as a square scipy CSR matrix in canonical form (rows ascending, no repeated entry): the kernels sum a row in
+    ascending column order.  The caller's matrix is never changed."""
+    from scipy import sparse
+
+    _assert_key_in_adata(adata, key, "obsp")
+    adj = adata.obsp[key]
+    adj = adj if sparse.isspmatrix_csr(adj) else sparse.csr_matrix(adj)
+    if adj.shape[0] != adj.shape[1] or adj.shape[0] != adata.n_obs:
+        raise ValueError(f"Expected `adata.obsp[{key!r}]` of shape `{(adata.n_obs, adata.n_obs)}`, found `{adj.shape}`.")
+    if not adj.has_canonical_format:
+        adj = adj.copy()
+        adj.sum_duplicates()
+    if adj.dtype not in (np.float32, np.float64):
+        adj = adj.astype(np.float64)
+    return adj
+
+
+def _check_distance(distance: Any) -> int:
+    if isinstance(distance, bool) or not isinstance(distance, numbers.Integral):
+        raise TypeError(f"Expected `distance` to be of type `int`, found `{type(distance).__name__}`.")
+    if distance < 1:
+        raise ValueError(f"'distance' must be at least 1, got {distance}")
+    if distance > MAX_DISTANCE:
+        raise NotImplementedError(f"The niche kernels support a `distance` of at most {MAX_DISTANCE}, found {distance}.")
+    return int(distance)
+
+
+def _feature_matrix(adata: Any) -> Any:
+    """``adata.X`` as the kernels take it: scipy CSR / CSC or a 2-D array, finite."""
+    from scipy import sparse
+
+    X = adata.X
+    if X is None:
+        raise ValueError("`adata.X` is `None`.")
+    if not sparse.issparse(X):
+        X = np.asarray(X)
+        if X.ndim != 2:
+            raise ValueError(f"Expected `adata.X` to be 2-D, found shape `{X.shape}`.")
+    if X.shape[0] != adata.n_obs:
+        raise ValueError(f"Expected `adata.X` to have {adata.n_obs} rows, found {X.shape[0]}.")
+    values = X.data if sparse.issparse(X) else X
+    if values.dtype.kind not in "fiub":
+        raise TypeError(f"Expected a numeric `adata.X`, found dtype `{values.dtype}`.")
+    if values.dtype.kind == "f" and not np.isfinite(values).all():
+        raise ValueError("`adata.X` contains NaN or infinity.")
+    return X
+
+
+def hop_weights(n_hop_weights: Any, distance: int) -> list[float] | None:
+    """The hop weights of ``_NhoodProfileEmbedder.get_embedding`` (gr/_niche.py:1185-1192): ``None`` -> ones, a short list is extended
+    with its last value (a new list: the caller's is not touched), a long one is kept whole — its surplus entries still count in
+    ``sum(weights)``, as in the reference."""
+    if distance == 1:
+        return None  # (the reference does not look at the weights)
+    if n_hop_weights is None:
+        return [1.0] * distance
+    if not isinstance(n_hop_weights, list):
+        raise TypeError(f"Expected `n_hop_weights` to be of type `list`, found `{type(n_hop_weights).__name__}`.")
+    if len(n_hop_weights) == 0:
+        raise ValueError("Expected `n_hop_weights` to hold at least one weight.")
+    weights = [float(w) for w in n_hop_weights]
+    if not np.isfinite(weights).all():
+        raise ValueError(f"Expected finite `n_hop_weights`, found `{n_hop_weights}`.")
+    if len(weights) < distance:
+        weights = weights + [weights[-1]] * (distance - len(weights))
+    return weights
+
+
+def combine_hop_profiles(hops: np.ndarray, weights: list[float] | None, abs_nhood: bool) -> np.ndarray:
+    """gr/_niche.py:1194-1214 on the hop profiles ``hops[h - 1]``: ``w0 * P1``, ``+= w_h * P_(h+1)`` hop by hop, then ``/ sum(weights)``
+    unless ``abs_nhood`` — numpy's elementwise operations in the reference's order.  One hop is returned as it is."""
+    if hops.shape[0] == 1:
+        return np.ascontiguousarray(hops[0])
+    profile = weights[0] * hops[0]
+    for h in range(1, hops.shape[0]):
+        profile += weights[h] * hops[h]
+    if not abs_nhood:
+        profile = profile / sum(weights)
+    return np.ascontiguousarray(profile)
+
+
+def niche_nhood_profile(
+    adata: Any,
+    groups: str,
+    spatial_connectivities_key: str = "spatial_connectivities",
+    distance: int = 1,
+    abs_nhood: bool = False,
+    n_hop_weights: list[float] | None = None,
+    *,
+    table_key: str | None = None,
+    device: int | None = None,
+) -> np.ndarray:
+    """The neighbourhood profile of the reference's ``neighborhood`` flavour: ``_NhoodProfileEmbedder.get_embedding`` with
+    ``scale=False`` (gr/_niche.py:1171-1221), an ``(n_obs, n_categories)`` C-contiguous float64 array with rows in ``adata.obs`` order
+    and columns in ``adata.obs[groups].cat.categories`` order (empty categories included).
+
+    Hop ``h`` (1 .. ``distance``) is ``A^h @ onehot(groups)`` with the graph's weights, computed on the GPU as ``A @ (A^(h-1) @ onehot)``
+    (the reference forms the sparse power ``A^h``).  With ``abs_nhood=False`` every hop's rows are divided by their sum (0/0 -> 0).
+    The hops are combined as ``w0 * P1 + w1 * P2 + ...`` and divided by ``sum(weights)`` unless ``abs_nhood``; ``n_hop_weights``
+    shorter than ``distance`` is extended with its last value (the list itself is not changed); any finite weights are accepted.
+    A column that is not categorical is converted for the call with the reference's warning; nothing is written into ``adata``.
+
+    Float64 throughout (float32 graph weights are widened exactly); every row sum runs in ascending column order with separately
+    rounded products and sums, so two calls return the same bytes.  The result is pinned to the reference run on a float64 graph: equal
+    on graphs of unit weights, within rounding of the reference's other summation order otherwise.
+
+    The reference's next step is ``sc.pp.scale(..., zero_center=True)`` (when ``scale=True``), then ``sc.pp.neighbors(use_rep="X")`` and
+    ``sc.tl.leiden``.  Under a process group every rank computes the whole result."""
+    adata = extract_adata_if_sdata(adata, table_key=table_key)
+    # every refusal first: nothing has touched the device when one is raised
+    if not isinstance(groups, str):
+        raise TypeError(f"Expected `groups` to be of type `str`, found `{type(groups).__name__}`.")
+    _assert_key_in_adata(adata, groups, "obs")
+    distance = _check_distance(distance)
+    weights = hop_weights(n_hop_weights, distance)
+    adj = _canonical_graph(adata, spatial_connectivities_key)
+    column = adata.obs[groups]
+    if column.dtype.name != "category":
+        warnings.warn(NOT_CATEGORICAL_MSG, stacklevel=2)
+        column = column.astype("category")  # a copy: `adata.obs` keeps its column
+    n_categories = len(column.cat.categories)
+    n = adata.n_obs
+    if n == 0 or n_categories == 0:
+        return np.zeros((n, n_categories), dtype=np.float64)
+    codes = np.ascontiguousarray(column.cat.codes.to_numpy(), dtype=np.int32)  # -1: no category (NaN)
+
+    ctx = default_context(device)
+    g = cached_graph(ctx, adj, with_data=True)
+    hops = niche_label_hops(ctx, g, codes, n_categories, distance, weighted=True, normalise=not abs_nhood)
+    return combine_hop_profiles(hops, weights, bool(abs_nhood))
+
+
+def niche_utag_features(
+    adata: Any,
+    spatial_connectivities_key: str = "spatial_connectivities",
+    *,
+    table_key: str | None = None,
+    device: int | None = None,
+) -> np.ndarray:
+    """The feature matrix of the reference's ``utag`` flavour, ``normalize(A, norm="l1", axis=1) @ adata.X`` (gr/_niche.py:1259-1260),
+    as an ``(n_obs, n_vars)`` C-contiguous float64 array: the rows of the graph are divided by their L1 norm (a row of norm 0 stays
+    as it is) and multiplied by ``adata.X`` on the GPU.  ``adata.X`` may be dense, CSR or CSC, float32 or float64; it is densified on
+    the device one block of columns at a time.
+
+    Float64 throughout (float32 is widened exactly; the reference's result dtype follows its inputs); every row sum runs in ascending
+    column order with separately rounded products and sums.  The result is pinned to the reference run on ``.astype(float64)`` inputs.
+    Nothing is written into ``adata``.
+
+    The reference's next step is ``sc.tl.pca`` on this matrix, then ``sc.pp.neighbors`` and ``sc.tl.leiden``.  Under a process group
+    every rank computes the whole result."""
+    adata = extract_adata_if_sdata(adata, table_key=table_key)
+    adj = _canonical_graph(adata, spatial_connectivities_key)
+    X = _feature_matrix(adata)
+    out = np.zeros((adata.n_obs, X.shape[1]), dtype=np.float64)
+    if out.size == 0:
+        return out
+    ctx = default_context(device)
+    g = cached_graph(ctx, adj, with_data=True)
+    m = DeviceMatrix(ctx, X)
+    try:
+        niche_aggregate(ctx, m, out, graph=g)
+    finally:
+        m.close()
+    return out
+
+
+def _unit_graph(adata: Any, key: str) -> Any:
+    adj = _canonical_graph(adata, key)
+    if adj.nnz and not (adj.data == 1).all():
+        raise NotImplementedError(
+            "The CellCharter hop shells need a graph whose stored values are all 1 (what every builder returns with `transform=None`): "
+            "the reference compares float path sums of a weighted graph against visit counts, which has no meaning worth pinning."
+        )
+    return adj
+
+
+def hop_shells(adj: Any, distance: int, *, device: int | None = None, count_limit: int = 0) -> "list[tuple[Any, Any]]":
+    """``[(hop_k, vis_k) for k = 1 .. distance]`` of the reference's ``_hop`` recurrence (see ``niche_cellcharter_features``) as scipy
+    CSR matrices, built on the GPU; ``adj`` a canonical CSR matrix of ones.  ``count_limit`` lowers the path count limit of 2**24."""
+    ctx = default_context(device)
+    shells = HopShells(ctx, cached_graph(ctx, adj, with_data=False), distance, count_limit)
+    try:
+        return [shells.read(k) for k in range(1, distance + 1)]
+    finally:
+        shells.close()
+
+
+def niche_cellcharter_features(
+    adata: Any,
+    distance: int = 3,
+    aggregation: str = "mean",
+    spatial_connectivities_key: str = "spatial_connectivities",
+    *,
+    table_key: str | None = None,
+    device: int | None = None,
+) -> np.ndarray:
+    """The aggregated matrix of the reference's ``cellcharter`` flavour with ``use_rep=None`` — ``arr`` of gr/_niche.py:1336-1355, in
+    front of the PCA — as an ``(n_obs, (distance + 1) * n_vars)`` C-contiguous float64 array.  Block 0 is ``adata.X``; block ``k`` is
+    ``D_k^-1 hop_k X`` for ``"mean"`` and ``D_k^-1 hop_k X^2 - (D_k^-1 hop_k X)^2`` for ``"variance"``, ``D_k`` the row sums of
+    ``hop_k`` (1/0 -> 0).
+
+    The shells follow the reference's ``_setdiag`` / ``_hop`` literally, which is NOT a breadth-first search.  With ``vis_1 = A`` with
+    its diagonal set to 1 and ``hop_1 = A`` without its diagonal::
+
+        P_k   = hop_{k-1} @ A        # path counts; self loops of A take part
+        hop_k = P_k > vis_{k-1}      # elementwise, an absent entry is 0
+        vis_k = vis_{k-1} + hop_k
+
+    so a node visited before re-enters shell ``k`` whenever more paths reach it than it has been visited: on a hexagonal lattice every
+    1-hop neighbour is in shell 2 again.  The shells are built on the GPU as sorted CSR with 32-bit integer path counts.
+
+    Every stored value of the graph must be 1 (``NotImplementedError`` otherwise), and a path count that reaches 2**24 — where the
+    reference's float32 sums stop being exact — raises ``NotImplementedError``.  An invalid ``aggregation`` raises the reference's
+    ``ValueError``.  Float64 throughout (float32 ``X`` is widened exactly; the reference's result dtype is an accident of its inputs);
+    row sums in ascending column order, products and sums rounded separately, variance as ``m2 - m1 * m1``.  The result is pinned to
+    the reference run on ``.astype(float64)`` inputs.  Nothing is written into ``adata``.
+
+    The reference's next step is ``sc.tl.pca`` on this matrix, then the Gaussian mixture (``gmm_fit`` takes up to 64 columns of it).
+    Under a process group every rank computes the whole result."""
+    adata = extract_adata_if_sdata(adata, table_key=table_key)
+    distance = _check_distance(distance)
+    if aggregation not in ("mean", "variance"):
+        raise ValueError(f"Invalid aggregation method '{aggregation}'. Please choose either 'mean' or 'variance'.")
+    adj = _unit_graph(adata, spatial_connectivities_key)
+    X = _feature_matrix(adata)
+    n, nv = adata.n_obs, X.shape[1]
+    out = np.zeros((n, (distance + 1) * nv), dtype=np.float64)
+    if out.size == 0:
+        return out
+    ctx = default_context(device)
+    g = cached_graph(ctx, adj, with_data=False)
+    m = DeviceMatrix(ctx, X)
+    shells = None
+    try:
+        try:
+            shells = HopShells(ctx, g, distance)
+        except SqgrError as exc:
+            if exc.status == -4:  # SQGR_ERR_UNSUPPORTED
+                raise NotImplementedError(str(exc)) from None
+            raise
+        for k in range(distance + 1):
+            niche_aggregate(ctx, m, out[:, k * nv : (k + 1) * nv], shells=shells, k=k, variance=aggregation == "variance")
+    finally:
+        if shells is not None:
+            shells.close()
+        m.close()
+    return out
