@@ -206,6 +206,27 @@ __host__ __device__ inline uint32_t grouped_perm(uint32_t x, const FeistelDomain
     return a * d.B + b;
 }
 
+// The inverse rounds, single-permutation form.  Every round adds a function of the OTHER digit, so it is undone by subtracting
+// the same value: the networks are bijections of A x B with closed-form inverses (k_shuffle_fix; tests/test_shuffle_fix_cpu.py).
+// b <- (b - F_B(a, k)) mod B:  F_B <= Bmask < 2B is reduced by one conditional subtraction first, as feistel_F1's callers do
+__host__ __device__ inline uint32_t feistel_unadd_b(uint32_t b, uint32_t a, uint32_t k, const FeistelDomain& d) {
+    uint32_t f = feistel_F1(a, k, d.bsh);
+    f = f >= d.B ? f - d.B : f;
+    return b >= f ? b - f : b + d.B - f;
+}
+// sigma_p backwards: the high digit's round first
+__host__ __device__ inline void sigma_inverse(uint32_t& a, uint32_t& b, const FeistelDomain& d, uint32_t k0, uint32_t k1) {
+    a = (a - feistel_F1(b, k1, d.ash)) & (d.A - 1u);
+    b = feistel_unadd_b(b, a, k0, d);
+}
+// one pass of the eight rounds backwards (rk: the keys of feistel_perm / grouped_perm's pi; the low 16 bits are used)
+__host__ __device__ inline void feistel_rounds_inverse(uint32_t& a, uint32_t& b, const FeistelDomain& d, const uint32_t* rk) {
+    for (int r = FEISTEL_ROUNDS - 2; r >= 0; r -= 2) {
+        b = feistel_unadd_b(b, a, rk[r + 1], d);
+        a = (a - feistel_F1(b, rk[r], d.ash)) & (d.A - 1u);
+    }
+}
+
 // single-permutation form (same arithmetic): image of x (< n)
 __host__ __device__ inline uint32_t feistel_perm(uint32_t x, const FeistelDomain& d, const uint32_t* rk) {
     uint32_t a = x / d.B, b = x - a * d.B;

@@ -51,6 +51,36 @@ __device__ __forceinline__ void slab_store16(uint8_t* __restrict__ batch_base, i
     }
 }
 
+// where slab_store16 puts label j < 16 of spot i, as a byte offset from batch_base: plane j / pw, row i, byte j % pw
+__host__ __device__ inline size_t slab_label_offset(int64_t n, int64_t i, int pw, int j) {
+    return (size_t)(j / pw) * (size_t)n * pw + (size_t)i * pw + (size_t)(j % pw);
+}
+
+// k_shuffle_fix's work for ONE out-of-range rank y in [n, A*B) and one permutation (gk: the 8 keys of its group, k0 | k1: its
+// sigma keys; 16 bits each): the spot whose FIRST sigma image is y and the rank sigma's cycle walk ends on — or false when no
+// spot's first image is y (sigma^-1(y) lies outside [0, n) itself; y is then reached only from another out-of-range rank, and
+// that rank's call owns the spot).  sigma and pi_g are bijections of A x B, so over all y the spots returned are exactly those
+// whose first image leaves [0, n), each once; the inverse of a cycle-walked permutation is the cycle-walked inverse.
+__host__ __device__ inline bool shuffle_fix_target(uint32_t y, const FeistelDomain& d, const uint32_t* gk, uint32_t k0, uint32_t k1,
+                                                   uint32_t* spot, uint32_t* rank_out) {
+    const uint32_t ya = y / d.B, yb = y - ya * d.B;
+    uint32_t a = ya, b = yb;
+    sigma_inverse(a, b, d, k0, k1);
+    if (a * d.B + b >= d.n) return false;
+    do feistel_rounds_inverse(a, b, d, gk); while (a * d.B + b >= d.n);  // pi_g^-1, cycle-walked: the walk started inside [0, n)
+    *spot = a * d.B + b;
+    a = ya;
+    b = yb;
+    do {  // forward as the exact route of k_shuffle: sigma until the image is back inside (its cycle holds sigma^-1(y) < n)
+        uint32_t t = b + feistel_F1(a, k0, d.bsh);
+        t = t >= d.B ? t - d.B : t;
+        b = t >= d.B ? t - d.B : t;
+        a = (a + feistel_F1(b, k1, d.ash)) & (d.A - 1u);
+    } while (a * d.B + b >= d.n);
+    *rank_out = a * d.B + b;
+    return true;
+}
+
 // every label in [0, K) (allow_negative: or below 0 — unlabelled), else an error that names the first offender
 int check_labels(const int32_t* labels, int64_t n, int K, bool allow_negative);
 
@@ -76,6 +106,7 @@ struct LabelShuffler {
     PcgWorkspace pcg_ws;        // jump-ahead table and row workspace of the numpy-compatible shuffle (sqgr_pcg.hip)
     bool has_labels = false;
     int max_label_count = 0;    // largest cluster of the base labels (0: unknown — injected label vectors)
+    const char* fix_why = nullptr;  // why these tables keep k_shuffle_tab's sentinel test (NULL: the FIX pair may run — create)
     bool wide() const { return K > 256; }  // 16-bit labels
     bool mapped() const { return spot_of.p != nullptr; }
 

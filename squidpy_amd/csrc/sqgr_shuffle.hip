@@ -6,7 +6,10 @@
 //   k_shuffle_tab : the same labels for 16-wide rows without libraries on up to 2^20 spots, at launch-group size: the first
 //               round of the per-permutation network depends on the spot only through the high digit of its group image, so
 //               each block tabulates it in LDS per row pair (64 KB) and a spot reads it back — 3 packed instructions per
-//               permutation pair instead of 10 (launch_shuffle_raw selects; SQGR_SHUFFLE_TABLE=0|1|2).
+//               permutation pair instead of 10 (launch_shuffle_raw selects; SQGR_SHUFFLE_TABLE=0|1|2).  On tables whose only
+//               sentinel labels are the ranks >= n it runs without the sentinel test, and
+//   k_shuffle_fix : behind it, thread per out-of-range rank and permutation, writes the labels whose first sigma image left
+//               [0, n) from the inverse networks (SQGR_SHUFFLE_FIX=0|2).
 // The numpy streams (PCG64 + Generator.shuffle) are sqgr_pcg.hip's; k_gather_labels16 applies their permutations to 16-bit labels.
 #include "sqgr_shuffle.h"
 
@@ -289,15 +292,28 @@ __device__ __forceinline__ uint32_t first_label(uint32_t e, uint32_t bpk, uint32
 
 // NOMAP: no spot map — the rank of slab row i is i itself, and its digits (a0, b0) advance with the grid stride instead of being
 // divided out per spot.
-template <bool SMALLK, bool NOMAP>
+// FIX (launch_shuffle_raw decides; SQGR_SHUFFLE_FIX): no sentinel test and no exact route.  The only labels that need the route
+// on an eligible table (LabelShuffler::fix_why) are those whose first sigma image is one of the A*B - n ranks outside [0, n) —
+// 4.5e-4 of them at 1e6 spots, which a WAVE nevertheless met in 11 % of its words — and k_shuffle_fix, launched behind this
+// kernel, writes exactly those from the inverse networks.  Here the entries of the blocks that reach past rank n (the partial
+// block, which eligibility requires to end in label K - 1, and with B clamped to 16 whole blocks behind it) are replaced while
+// the table is copied into LDS by  K - 1 | 0xFFFF << 16 : every byte this kernel stores is a label < K, whatever runs later.
+template <bool SMALLK, bool NOMAP, bool FIX>
 __global__ __launch_bounds__(SHUF_TAB_THREADS, 8) void k_shuffle_tab(int64_t n, const uint32_t* __restrict__ cum, int kpad, int blk_words, int K,
                                                                   const uint32_t* __restrict__ keys, LibDom dom0, int nrows,
                                                                   uint8_t* __restrict__ slab_all, int pw, const int32_t* __restrict__ spot_of,
                                                                   int tab_word0) {
+    static_assert(!FIX || (SMALLK && NOMAP), "the FIX pair runs without a spot map and with K <= 126 only");
     extern __shared__ uint32_t s_lds[];
     uint32_t* s_cum = s_lds + blk_words;
-    for (int t = threadIdx.x; t < kpad; t += SHUF_TAB_THREADS) s_cum[t] = cum[t];
-    for (int t = threadIdx.x; t < blk_words; t += SHUF_TAB_THREADS) s_lds[t] = cum[kpad + t];
+    if constexpr (FIX) {  // (the boundaries are the exact route's: not read here)
+        const int past = (int)((uint32_t)n / dom0.dom.B);  // first block that holds a rank >= n
+        for (int t = threadIdx.x; t < blk_words; t += SHUF_TAB_THREADS)
+            s_lds[t] = t >= past ? ((uint32_t)(K - 1) | (0xFFFFu << 16)) : cum[kpad + t];
+    } else {
+        for (int t = threadIdx.x; t < kpad; t += SHUF_TAB_THREADS) s_cum[t] = cum[t];
+        for (int t = threadIdx.x; t < blk_words; t += SHUF_TAB_THREADS) s_lds[t] = cum[kpad + t];
+    }
     const FeistelDomain dom = dom0.dom;
     const int row0 = 2 * blockIdx.y;
     const int row1 = min(row0 + 1, nrows - 1);  // an odd last row is paired with itself (stored once)
@@ -414,7 +430,9 @@ __global__ __launch_bounds__(SHUF_TAB_THREADS, 8) void k_shuffle_tab(int64_t n, 
                 }
             }
             bool sentinel;
-            if constexpr (SMALLK) {
+            if constexpr (FIX) {  // no label is K: the table holds none, and k_shuffle_fix rewrites the images outside [0, n)
+                sentinel = false;
+            } else if constexpr (SMALLK) {
                 sentinel = ((word + sent_add) & 0x80808080u) != 0;
             } else {  // K = 256 has no sentinel value left in a byte: every label takes the exact route
                 const uint32_t k = (uint32_t)K;
@@ -456,6 +474,32 @@ __global__ __launch_bounds__(SHUF_TAB_THREADS, 8) void k_shuffle_tab(int64_t n, 
     slab_store16(slab_all + (size_t)row0 * n * 16, n, i, pw, outA[0], outA[1], outA[2], outA[3]);
     if (store1) slab_store16(slab_all + (size_t)row1 * n * 16, n, i, pw, outB[0], outB[1], outB[2], outB[3]);
     }
+}
+
+// Behind k_shuffle_tab<true, true, true>: the labels whose first sigma image left [0, n).  They are not searched for: one thread
+// per (row, permutation j < 16, out-of-range rank y = n + e, e < E = A*B - n) inverts both networks to the spot whose first
+// image is y (shuffle_fix_target), walks sigma forward from y as the exact route does, ranks the end of the walk against the
+// boundaries (cum[K] = UINT_MAX) and stores that one byte where slab_store16 put the spot's label j.  No lists, no atomics:
+// every affected (spot, permutation) is reached by exactly one thread and no other byte is touched.  448 x 16 threads per row at
+// 1e6 spots against 1e6 x 16 labels.
+__global__ __launch_bounds__(256) void k_shuffle_fix(int64_t n, const uint32_t* __restrict__ cum, int K, const uint32_t* __restrict__ keys,
+                                                     FeistelDomain dom, int nrows, uint32_t E, uint8_t* __restrict__ slab_all, int pw) {
+    const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (t >= (int64_t)nrows * FEISTEL_GROUP * E) return;
+    const uint32_t e = (uint32_t)(t % E);
+    const int j = (int)((t / E) % FEISTEL_GROUP);
+    const int64_t row = t / ((int64_t)E * FEISTEL_GROUP);
+    const uint32_t* krow = keys + (size_t)row * key_words_per_row(16, 1);  // group keys (both halves alike), then sigma's pairs
+    const uint32_t* sk = krow + 8 + (j >> 1) * 2;
+    const int sh = (j & 1) * 16;
+    uint32_t spot, x;
+    if (!shuffle_fix_target(dom.n + e, dom, krow, (sk[0] >> sh) & 0xFFFFu, (sk[1] >> sh) & 0xFFFFu, &spot, &x)) return;
+    uint32_t lo = 0, hi = (uint32_t)K - 1u;  // the label of rank x: the first l with x < cum[l + 1]
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (x < cum[mid + 1]) hi = mid; else lo = mid + 1;
+    }
+    slab_all[(size_t)row * n * 16 + slab_label_offset(n, spot, pw, j)] = (uint8_t)lo;
 }
 
 // The generator WITHOUT its shortcut (what do 16 independent bijections cost?): slab label b of row `row` =
@@ -754,6 +798,21 @@ int LabelShuffler::create(sqgr_ctx* ctx, int64_t n, const int32_t* labels, int K
             blk[doms[l].aoff + a] = word;
         }
     }
+    // k_shuffle_tab's FIX pair drops the sentinel test: these tables qualify when the only sentinel labels left are the ranks >= n
+    if (libs_on) {
+        p->fix_why = "libraries (per-library domains and keys)";
+    } else if (K > 126) {
+        p->fix_why = "more than 126 clusters";
+    } else {
+        const FeistelDomain& d = doms[0].dom;
+        const uint32_t past = (uint32_t)n / d.B;  // first block that holds a rank >= n
+        for (uint32_t a = 0; a < past && a < d.A && !p->fix_why; ++a)
+            if ((blk[a] & 0xFFu) == (uint32_t)K)  // byte 0 (byte 1 of such a word holds the block's first label)
+                p->fix_why = "a block of the label-sorted base has several label starts or skips an empty category (lab0 = K)";
+        const uint32_t tail = (uint32_t)n - past * d.B;  // ranks of the partial block inside [0, n)
+        if (!p->fix_why && tail > 0 && blk[past] != ((uint32_t)(K - 1) | (tail << 16)))
+            p->fix_why = "the block that reaches past the last rank does not end in label K - 1 in two-field form";
+    }
     cum.insert(cum.end(), blk.begin(), blk.end());
     p->dom0.dom = make_domain((uint32_t)n);
     p->dom0.aoff = 0;
@@ -826,8 +885,14 @@ int LabelShuffler::launch_shuffle_raw(int B, int nb, const uint32_t* keys, uint8
     const char* env_blocks = getenv("SQGR_SHUFFLE_BLOCKS_PER_CU");
     if (env_blocks && atoi(env_blocks) > 0) per_cu = atoi(env_blocks);
     gx = std::min<unsigned>(gx, (unsigned)(per_cu * std::max(ctx->cu_count, 1)) / (unsigned)std::max(nb, 1) + 1);
+    const char* env_fix = getenv("SQGR_SHUFFLE_FIX");
+    const int fix_mode = env_fix ? atoi(env_fix) : -1;
+    if (fix_mode == 2 && (wide() || independent)) {
+        set_error("SQGR_SHUFFLE_FIX=2: the launch is not eligible: %s", wide() ? "more than 126 clusters" : "SQGR_SHUFFLE_INDEPENDENT=1");
+        return SQGR_ERR_UNSUPPORTED;
+    }
     LaunchTimer t(ctx, wide() ? "nhood_shuffle16" : "nhood_shuffle", st);
-    const size_t lds = (tab_lds ? (size_t)n_libs * kpad * 4 : 0) + (size_t)blk_words * 4;
+    const size_t lds =(tab_lds ? (size_t)n_libs * kpad * 4 : 0) + (size_t)blk_words * 4;
     if (wide()) {
         if (B != 16) {
             set_error("more than 256 clusters: 16 permutations per pass only");
@@ -881,7 +946,16 @@ int LabelShuffler::launch_shuffle_raw(int B, int nb, const uint32_t* keys, uint8
         const int cus = std::max(ctx->cu_count, 1);
         const int64_t block_trips = ceil_div(n, SHUF_TAB_THREADS) * (int64_t)gy;  // (block, trip) units of the launch
         const bool big = block_trips >= (int64_t)SHUF_TAB_MIN_TRIPS * 2 * cus;
-        if (!why && mode != 0 && (mode == 1 || mode == 2 || big)) {
+        // the FIX pair (k_shuffle_tab without its sentinel test, k_shuffle_fix behind it).  SQGR_SHUFFLE_FIX (read at every call):
+        // 0 never, 2 required — the table kernel then takes an eligible input whatever the launch size, and a launch that is not
+        // eligible is an error that names the reason —, unset: whenever the table kernel runs on eligible tables
+        const char* fix_no = why ? why : mode == 0 ? "SQGR_SHUFFLE_TABLE=0" : spot_of.p ? "a spot map (the rank is not the slab row)" : fix_why;
+        if (fix_mode == 2 && fix_no) {
+            set_error("SQGR_SHUFFLE_FIX=2: the launch is not eligible: %s", fix_no);
+            return SQGR_ERR_UNSUPPORTED;
+        }
+        const bool fix = fix_mode != 0 && !fix_no;
+        if (!why && mode != 0 && (mode == 1 || mode == 2 || big || fix_mode == 2)) {
             int tab_per_cu = SHUF_TAB_BLOCKS_PER_CU;
             if (env_blocks && atoi(env_blocks) > 0) tab_per_cu = atoi(env_blocks);
             // grid cap as for k_shuffle, then the same number of trips for every block (105 600 spots x 160 rows: 104 blocks' worth
@@ -891,19 +965,27 @@ int LabelShuffler::launch_shuffle_raw(int B, int nb, const uint32_t* keys, uint8
             const unsigned cap = (unsigned)(tab_per_cu * cus) / gy + 1;
             const unsigned trips = (nblk + cap - 1) / cap;
             const unsigned tx = (nblk + trips - 1) / trips;
-#define SQGR_SHUFFLE_TAB(SK, NOMAP)                                                                                             \
-    do {                                                                                                                       \
-        SQGR_TRY(allow_lds(k_shuffle_tab<SK, NOMAP>, lds_tab));                                                                \
-        k_shuffle_tab<SK, NOMAP><<<dim3(tx, gy), SHUF_TAB_THREADS, lds_tab, st>>>(n, cum.p, kpad, blk_words, K, keys, dom0, nb, \
-                                                                                slab, pw, spot_of.p, (int)tab_word0);        \
+#define SQGR_SHUFFLE_TAB(SK, NOMAP, FIX)                                                                                            \
+    do {                                                                                                                           \
+        SQGR_TRY(allow_lds(k_shuffle_tab<SK, NOMAP, FIX>, lds_tab));                                                               \
+        k_shuffle_tab<SK, NOMAP, FIX><<<dim3(tx, gy), SHUF_TAB_THREADS, lds_tab, st>>>(n, cum.p, kpad, blk_words, K, keys, dom0, nb, \
+                                                                                     slab, pw, spot_of.p, (int)tab_word0);       \
     } while (0)
-            if (K <= 126) {
-                if (spot_of.p) SQGR_SHUFFLE_TAB(true, false); else SQGR_SHUFFLE_TAB(true, true);
+            if (fix) {
+                SQGR_SHUFFLE_TAB(true, true, true);
+            } else if (K <= 126) {
+                if (spot_of.p) SQGR_SHUFFLE_TAB(true, false, false); else SQGR_SHUFFLE_TAB(true, true, false);
             } else {
-                if (spot_of.p) SQGR_SHUFFLE_TAB(false, false); else SQGR_SHUFFLE_TAB(false, true);
+                if (spot_of.p) SQGR_SHUFFLE_TAB(false, false, false); else SQGR_SHUFFLE_TAB(false, true, false);
             }
 #undef SQGR_SHUFFLE_TAB
             SQGR_HIP(hipGetLastError());
+            const uint32_t E = A * dom0.dom.B - (uint32_t)n;  // ranks of the domain outside [0, n)
+            if (fix && E > 0) {  // same stream, inside this launch's timer bracket: its time is the shuffle's
+                const int64_t threads = (int64_t)nb * FEISTEL_GROUP * E;
+                k_shuffle_fix<<<(unsigned)ceil_div(threads, 256), 256, 0, st>>>(n, cum.p, K, keys, dom0.dom, nb, E, slab, pw);
+                SQGR_HIP(hipGetLastError());
+            }
             return SQGR_OK;
         }
     }
