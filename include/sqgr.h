@@ -478,6 +478,35 @@ int sqgr_niche_aggregate(sqgr_ctx* ctx, const sqgr_graph* g, const sqgr_shells* 
 int sqgr_niche_label_hops(sqgr_ctx* ctx, const sqgr_graph* g, const int32_t* labels, int32_t K, int32_t distance, int32_t weighted,
                           int32_t normalise, double* out);
 
+/* ---- PCA of a dense matrix resident on the device: the parts of scanpy's default `sc.tl.pca` that grow with n ---------------------
+ * (sklearn's `PCA(n_components, svd_solver="arpack")`, what the reference's utag and cellcharter flavours call next: gr/_niche.py
+ * :1262, :1357.)  The handle owns F, float64[n][D] row-major, on the device.  The caller diagonalises the D x D scatter matrix on
+ * the host between sqgr_pca_moments and sqgr_pca_project.  Float64 throughout, no float atomics, no FMA; every order of summation
+ * depends on (n, D) alone, so two calls return the same bytes.
+ *
+ * sqgr_pca_info: out_info int64[4] = {rows of a chunk of the row sums (chunks hold a multiple of it), largest D, largest c, columns
+ *   of a scatter tile}.  Needs no device.
+ * sqgr_pca_create: F zeroed.  SQGR_ERR_UNSUPPORTED unless 2 <= n < 2^31 and 2 <= D <= 4096.
+ * sqgr_pca_upload: F[:, col0 : col0 + n_cols] = x, a HOST row-major matrix of n rows, ld values apart, of value_bytes 8 (float64)
+ *   or 4 (float32, widened exactly).
+ * sqgr_pca_fill_aggregate: the block sqgr_niche_aggregate(ctx, g, shells, k, m, variance, ...) returns — same arguments, kernels and
+ *   arithmetic — written to F[:, col0 : col0 + m.n_cols] on the device instead of a host array.
+ * sqgr_pca_moments: out_mean float64[D], mean_j = (sum_i F[i][j]) / n, a fixed-order sum and one division;  out_scatter
+ *   float64[D][D], S[a][b] = sum_i (F[i][a] - mean_a) * (F[i][b] - mean_b): the mean is subtracted before the product, the sum is
+ *   not divided, and S is exactly symmetric.
+ * sqgr_pca_project: out float64[n][c] (HOST), out[i][r] = sum_j (F[i][j] - mean_j) * components[r][j] with j ascending and the mean
+ *   of the last sqgr_pca_moments (SQGR_ERR_INVALID when F was written since); components float64[c][D] on the host.
+ *   SQGR_ERR_UNSUPPORTED unless 1 <= c <= 64 and c < min(n, D). */
+typedef struct sqgr_pca sqgr_pca;
+int sqgr_pca_info(int64_t* out_info);
+int sqgr_pca_create(sqgr_ctx* ctx, int64_t n, int32_t D, sqgr_pca** out);
+int sqgr_pca_upload(sqgr_pca* h, const void* x, int32_t value_bytes, int64_t ld, int32_t col0, int32_t n_cols);
+int sqgr_pca_fill_aggregate(sqgr_pca* h, int32_t col0, const sqgr_graph* g, const sqgr_shells* shells, int32_t k, const sqgr_matrix* m,
+                            int32_t variance);
+int sqgr_pca_moments(sqgr_pca* h, double* out_mean, double* out_scatter);
+int sqgr_pca_project(sqgr_pca* h, const double* components, int32_t c, double* out);
+int sqgr_pca_destroy(sqgr_pca* h);
+
 #ifdef __cplusplus
 }
 #endif

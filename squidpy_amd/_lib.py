@@ -119,6 +119,13 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "sqgr_shells_destroy": (C.c_int, [C.c_void_p]),
     "sqgr_niche_aggregate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, c_f64p, C.c_int64]),
     "sqgr_niche_label_hops": (C.c_int, [C.c_void_p, C.c_void_p, c_i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_f64p]),
+    "sqgr_pca_info": (C.c_int, [c_i64p]),
+    "sqgr_pca_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]),
+    "sqgr_pca_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
+    "sqgr_pca_fill_aggregate": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "sqgr_pca_moments": (C.c_int, [C.c_void_p, c_f64p, c_f64p]),
+    "sqgr_pca_project": (C.c_int, [C.c_void_p, c_f64p, C.c_int32, c_f64p]),
+    "sqgr_pca_destroy": (C.c_int, [C.c_void_p]),
 }
 
 
@@ -905,6 +912,64 @@ def niche_label_hops(ctx: Context, g: Graph, labels: np.ndarray, n_cls: int, dis
     _check(ctx.lib, ctx.lib.sqgr_niche_label_hops(ctx.h, g.h, _ptr(labels, c_i32p), int(n_cls), int(distance), int(weighted), int(normalise),
                                                   _ptr(out, c_f64p)))
     return out
+
+
+def pca_info() -> dict[str, int]:
+    """Constants of ``csrc/sqgr_pca.hip`` (``sqgr_pca_info``); needs the library, not a device."""
+    lib = load_library()
+    out = np.zeros(4, dtype=np.int64)
+    _check(lib, lib.sqgr_pca_info(_ptr(out, c_i64p)))
+    return {"chunk_rows": int(out[0]), "max_features": int(out[1]), "max_components": int(out[2]), "tile_columns": int(out[3])}
+
+
+class DevicePCA:
+    """A dense float64 matrix ``F[n][D]`` resident on the device and the parts of a PCA that grow with ``n`` (``sqgr_pca``): its
+    column means and centred scatter matrix, and the projection on components the caller found from them."""
+
+    def __init__(self, ctx: Context, n: int, d: int):
+        self.ctx, self.n, self.d = ctx, int(n), int(d)
+        h = C.c_void_p()
+        _check(ctx.lib, ctx.lib.sqgr_pca_create(ctx.h, self.n, self.d, C.byref(h)))
+        self.h = h
+
+    def upload(self, x: np.ndarray, col0: int = 0) -> None:
+        """``F[:, col0 : col0 + x.shape[1]] = x``; ``x`` float64 or float32 with contiguous rows (a column range of a wider array)."""
+        if x.ndim != 2 or x.shape[0] != self.n or x.dtype not in (np.float32, np.float64) or x.strides[1] != x.itemsize or x.strides[0] % x.itemsize:
+            raise ValueError(f"Expected a float32 / float64 array of {self.n} rows with contiguous rows.")
+        _check(self.ctx.lib, self.ctx.lib.sqgr_pca_upload(self.h, C.c_void_p(x.ctypes.data), x.itemsize, max(x.strides[0] // x.itemsize, x.shape[1]),
+                                                          int(col0), x.shape[1]))
+
+    def fill_aggregate(self, col0: int, m: "DeviceMatrix", *, graph: Graph | None = None, shells: HopShells | None = None, k: int = 0,
+                       variance: bool = False) -> None:
+        """The block ``niche_aggregate`` returns, written into ``F[:, col0 : col0 + m.shape[1]]`` on the device."""
+        _check(self.ctx.lib, self.ctx.lib.sqgr_pca_fill_aggregate(self.h, int(col0), graph.h if graph is not None else None,
+                                                                  shells.h if shells is not None else None, int(k), m.h, int(variance)))
+
+    def moments(self) -> tuple[np.ndarray, np.ndarray]:
+        """``(mean[D], scatter[D][D])``: the column means and ``sum_i (x_i - mean)(x_i - mean)^T``, not divided."""
+        mean, scatter = np.zeros(self.d, dtype=np.float64), np.zeros((self.d, self.d), dtype=np.float64)
+        _check(self.ctx.lib, self.ctx.lib.sqgr_pca_moments(self.h, _ptr(mean, c_f64p), _ptr(scatter, c_f64p)))
+        return mean, scatter
+
+    def project(self, components: np.ndarray) -> np.ndarray:
+        """``(F - mean) @ components.T`` with the mean of the last ``moments()``; ``components`` ``(c, D)``."""
+        components = _as(components, np.float64)
+        if components.ndim != 2 or components.shape[1] != self.d:
+            raise ValueError(f"Expected components of shape (c, {self.d}), found {components.shape}.")
+        out = np.zeros((self.n, components.shape[0]), dtype=np.float64)
+        _check(self.ctx.lib, self.ctx.lib.sqgr_pca_project(self.h, _ptr(components, c_f64p), components.shape[0], _ptr(out, c_f64p)))
+        return out
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            self.ctx.lib.sqgr_pca_destroy(self.h)
+            self.h = None
+
+    def __del__(self) -> None:  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class AutocorrPlan:

@@ -26,6 +26,7 @@
 //                for four sums, an entry's four values are one 32-byte read, and the result is copied out as it lies.
 // k_label_hop    one thread per (row, category): P_h = A P_{h-1} on an n x K panel, P_0 = onehot(labels).
 #include "sqgr_matrix.h"
+#include "sqgr_pca.h"
 
 #include <algorithm>
 #include <vector>
@@ -624,8 +625,10 @@ int sqgr_shells_destroy(sqgr_shells* h) {
     return SQGR_OK;
 }
 
-int sqgr_niche_aggregate(sqgr_ctx* ctx, const sqgr_graph* g, const sqgr_shells* shells, int32_t k, const sqgr_matrix* m, int32_t variance,
-                         double* out, int64_t ld_out) {
+// The body of sqgr_niche_aggregate and sqgr_pca_fill_aggregate: the same kernels and the same arithmetic; every block of columns ends
+// in one pitched copy, to the host array `out` (kind hipMemcpyDeviceToHost) or to a device matrix (hipMemcpyDeviceToDevice).
+static int aggregate_blocks(sqgr_ctx* ctx, const sqgr_graph* g, const sqgr_shells* shells, int32_t k, const sqgr_matrix* m, int32_t variance,
+                            double* out, int64_t ld_out, hipMemcpyKind kind) {
     SQGR_REQUIRE(ctx && m && out && (g != nullptr) != (shells != nullptr), "null argument, or both / neither of graph and shells");
     SQGR_REQUIRE(m->ctx == ctx && (!g || g->ctx == ctx) && (!shells || shells->ctx == ctx), "handle belongs to a different context");
     SQGR_REQUIRE(m->cols_pending <= 0, "the matrix is still being uploaded");
@@ -699,10 +702,24 @@ int sqgr_niche_aggregate(sqgr_ctx* ctx, const sqgr_graph* g, const sqgr_shells* 
             else k_aggregate<2, false><<<grid, NICHE_T, 0, st>>>(ptr, idx, w, scale.p, Xr.p, n, cp, Y.p);
             SQGR_HIP(hipGetLastError());
         }
-        SQGR_HIP(hipMemcpy2DAsync(out + c0, (size_t)ld_out * 8, mode != 0 ? Y.p : Xr.p, (size_t)cp * 8, (size_t)c * 8, (size_t)n, hipMemcpyDeviceToHost, st));
+        SQGR_HIP(hipMemcpy2DAsync(out + c0, (size_t)ld_out * 8, mode != 0 ? Y.p : Xr.p, (size_t)cp * 8, (size_t)c * 8, (size_t)n, kind, st));
         SQGR_HIP(hipStreamSynchronize(st));  // the buffers are reused by the next block
     }
     return SQGR_OK;
+}
+
+int sqgr_niche_aggregate(sqgr_ctx* ctx, const sqgr_graph* g, const sqgr_shells* shells, int32_t k, const sqgr_matrix* m, int32_t variance,
+                         double* out, int64_t ld_out) {
+    return aggregate_blocks(ctx, g, shells, k, m, variance, out, ld_out, hipMemcpyDeviceToHost);
+}
+
+int sqgr_pca_fill_aggregate(sqgr_pca* h, int32_t col0, const sqgr_graph* g, const sqgr_shells* shells, int32_t k, const sqgr_matrix* m,
+                            int32_t variance) {
+    SQGR_REQUIRE(h && m, "null argument");
+    SQGR_REQUIRE(m->n_rows == h->n, "the matrix has %lld rows, the PCA %lld", (long long)m->n_rows, (long long)h->n);
+    SQGR_REQUIRE(col0 >= 0 && (int64_t)col0 + m->n_cols <= h->D, "columns [%d, %d + %lld) outside [0, %d)", col0, col0, (long long)m->n_cols, h->D);
+    h->have_mean = false;
+    return aggregate_blocks(h->ctx, g, shells, k, m, variance, h->F.p + col0, h->D, hipMemcpyDeviceToDevice);
 }
 
 int sqgr_niche_label_hops(sqgr_ctx* ctx, const sqgr_graph* g, const int32_t* labels, int32_t K, int32_t distance, int32_t weighted,

@@ -13,11 +13,20 @@ from ._build import (
 from ._ligrec import PermutationTest, ligrec
 from ._mask import MultiPolygon, Polygon, mask_graph
 from ._nhood import NhoodEnrichmentResult, centrality_scores, interaction_matrix, nhood_enrichment
-from ._niche import calculate_niche_cellcharter, niche_cellcharter_features, niche_nhood_profile, niche_utag_features
+from ._niche import (
+    PCAResult,
+    calculate_niche_cellcharter,
+    niche_cellcharter_embedding,
+    niche_cellcharter_features,
+    niche_nhood_profile,
+    niche_pca,
+    niche_utag_embedding,
+    niche_utag_features,
+)
 from ._ppatterns import co_occurrence, spatial_autocorr
 from ._ripley import ripley
 from ._sepal import sepal
 
-__all__ = ["nhood_enrichment", "interaction_matrix", "centrality_scores", "calculate_niche_cellcharter", "niche_nhood_profile", "niche_utag_features", "niche_cellcharter_features", "NhoodEnrichmentResult", "co_occurrence", "spatial_autocorr", "ripley", "sepal", "ligrec", "PermutationTest", "spatial_neighbors",
+__all__ = ["nhood_enrichment", "interaction_matrix", "centrality_scores", "calculate_niche_cellcharter", "niche_nhood_profile", "niche_utag_features", "niche_cellcharter_features", "niche_pca", "niche_utag_embedding", "niche_cellcharter_embedding", "PCAResult", "NhoodEnrichmentResult", "co_occurrence", "spatial_autocorr", "ripley", "sepal", "ligrec", "PermutationTest", "spatial_neighbors",
            "spatial_neighbors_knn", "spatial_neighbors_delaunay", "spatial_neighbors_radius", "spatial_neighbors_grid", "spatial_neighbors_from_builder",
            "neighbors", "SpatialNeighborsResult", "mask_graph", "Polygon", "MultiPolygon"]

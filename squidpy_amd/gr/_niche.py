@@ -6,7 +6,10 @@ numpy's ``RandomState`` exactly as sklearn's ``check_random_state(random_state).
 ``csrc/sqgr_gmm.hip`` (``sqgr_gmm_fit``).  Neither this module nor the library imports sklearn.
 
 ``niche_nhood_profile``, ``niche_utag_features`` and ``niche_cellcharter_features`` are stage 1 of the reference's three niche flavours:
-the feature matrix each of them computes from the spatial graph and hands to scanpy (``csrc/sqgr_niche.hip``)."""
+the feature matrix each of them computes from the spatial graph and hands to scanpy (``csrc/sqgr_niche.hip``).  ``niche_pca`` is
+scanpy's default ``sc.tl.pca`` on such a matrix — sklearn's ``PCA(svd_solver="arpack")`` — with the means, the scatter matrix and the
+projection on the GPU (``csrc/sqgr_pca.hip``) and the D x D eigenproblem on the host; ``niche_utag_embedding`` and
+``niche_cellcharter_embedding`` run it on feature blocks that never leave the device."""
 
 from __future__ import annotations
 
@@ -17,15 +20,19 @@ from typing import Any, NamedTuple
 import numpy as np
 import pandas as pd
 
-from .._lib import DeviceMatrix, HopShells, SqgrError, cached_graph, default_context, niche_aggregate, niche_label_hops
+from .._lib import DeviceMatrix, DevicePCA, HopShells, SqgrError, cached_graph, default_context, niche_aggregate, niche_label_hops
 from .._lib import gmm_fit as _gmm_fit
 from .._utils import extract_adata_if_sdata, logg
 
 __all__ = ["calculate_niche_cellcharter", "gmm_fit", "gmm_init_rows", "GMMFit", "GMM_MAX_FEATURES", "GMM_MAX_COMPONENTS",
-           "niche_nhood_profile", "niche_utag_features", "niche_cellcharter_features", "hop_shells"]
+           "niche_nhood_profile", "niche_utag_features", "niche_cellcharter_features", "hop_shells", "niche_pca", "PCAResult",
+           "niche_utag_embedding", "niche_cellcharter_embedding", "pca_n_comps", "pca_components", "PCA_MAX_FEATURES",
+           "PCA_MAX_COMPONENTS"]
 
 GMM_MAX_FEATURES = 64    # GMM_MAX of csrc/sqgr_gmm.hip
 GMM_MAX_COMPONENTS = 64
+PCA_MAX_FEATURES = 4096  # PCA_MAX_D of csrc/sqgr_pca.hip
+PCA_MAX_COMPONENTS = 64  # PCA_MAX_C
 NOT_A_NICHE = "not_a_niche"
 NICHE_COLUMN = "cellcharter_niche"
 
@@ -183,6 +190,7 @@ def calculate_niche_cellcharter(
     table_key: str | None = None,
     *,
     device: int | None = None,
+    **options: Any,
 ) -> Any:
     """Compute niche assignments with the cellcharter flavour (drop-in for ``squidpy.gr.calculate_niche_cellcharter``,
     gr/_niche.py:402-462): a Gaussian mixture of ``n_components`` components on ``adata.obsm[use_rep][:, :n_components]``, fitted by EM
@@ -198,8 +206,16 @@ def calculate_niche_cellcharter(
 
     Two deliberate limits:
 
-    - ``use_rep=None`` raises ``NotImplementedError``.  That path aggregates ``adata.X`` over hop shells and runs scanpy's PCA in
-      front of the mixture; the reference itself warns that it is a proxy, and the PCA cannot be pinned here.
+    - ``use_rep=None`` raises ``NotImplementedError`` unless ``proxy_pca=True`` is passed — by keyword only, default ``False``; it is
+      the one option ``**options`` accepts (the named parameters are pinned to the reference's signature plus ``device``, so the
+      switch is not one of them; any other keyword is a ``TypeError``).  That path (gr/_niche.py:1332-1359) logs
+      the reference's warning that PCA is only a proxy, aggregates ``adata.X`` over ``distance`` hop shells
+      (``niche_cellcharter_features``), runs the default PCA on the result (``niche_pca``: 50 components, or ``min(n, D) - 1``) and fits
+      the mixture on ALL columns of that embedding — ``n_components`` is then the number of mixture components only.  Everything up
+      to the embedding stays on the device.  The PCA is float64 where scanpy rounds ``X_pca`` to float32 by default: the path is
+      pinned to the reference's features, sklearn's ``PCA(svd_solver="arpack")`` and ``GaussianMixture`` in float64.  With
+      ``library_key`` every library runs on its own rows of ``X`` and its own sub-graph ``adj[rows][:, rows]`` (the reference's
+      ``adata[lib_indices].copy()``).  ``proxy_pca=True`` together with a ``use_rep`` is a ``ValueError``.
     - A float32 representation is converted to float64 and fitted in float64; sklearn would keep float32.  The result is pinned to
       sklearn on ``X.astype(np.float64)``.
 
@@ -209,22 +225,48 @@ def calculate_niche_cellcharter(
 
     Returns ``None`` if ``inplace=True``, else a copy of ``adata`` with the column added."""
     orig_adata = extract_adata_if_sdata(data, table_key=table_key)
+    proxy_pca = bool(options.pop("proxy_pca", False))
+    if options:
+        raise TypeError(f"calculate_niche_cellcharter() got an unexpected keyword argument {next(iter(options))!r}")
     # every refusal first: nothing has touched the device or the caller's object when one is raised
-    if use_rep is None:
+    if proxy_pca and use_rep is not None:
+        raise ValueError("`proxy_pca=True` runs the `use_rep=None` path; found `use_rep={!r}`.".format(use_rep))
+    if use_rep is None and not proxy_pca:
         raise NotImplementedError(
             "calculate_niche_cellcharter needs `use_rep` here: the reference's `use_rep=None` path (hop-shell aggregation of `adata.X` and "
             "scanpy's PCA in front of the mixture) is not implemented."
         )
-    _assert_key_in_adata(orig_adata, use_rep, "obsm")
-    embedding = np.asarray(orig_adata.obsm[use_rep])
-    if embedding.shape[1] < n_components:
-        raise ValueError(
-            f"Embedding has {embedding.shape[1]} components, but n_components={n_components}. "
-            f"Please provide an embedding with at least {n_components} components."
-        )
-    if library_key is not None:
-        _assert_key_in_adata(orig_adata, library_key, "obs")
-    embedding = _validated_matrix(embedding[:, :n_components], n_components, check_rows=library_key is None)
+    if use_rep is None:
+        if library_key is not None:
+            _assert_key_in_adata(orig_adata, library_key, "obs")
+        distance = _check_distance(distance)
+        _check_aggregation(aggregation)
+        adj = _unit_graph(orig_adata, spatial_connectivities_key)
+        X = _feature_matrix(orig_adata)
+        if library_key is None:
+            _check_pca_shape(orig_adata.n_obs, (distance + 1) * X.shape[1], None)
+
+        def embed(rows: np.ndarray | None) -> np.ndarray:
+            logg.warning(PROXY_PCA_MSG)
+            if rows is None:
+                return _cellcharter_pca(adj, X, distance, aggregation, None, device).X_pca
+            sub = adj[rows][:, rows]
+            sub.sort_indices()
+            return _cellcharter_pca(sub, X[rows], distance, aggregation, None, device).X_pca
+    else:
+        _assert_key_in_adata(orig_adata, use_rep, "obsm")
+        embedding = np.asarray(orig_adata.obsm[use_rep])
+        if embedding.shape[1] < n_components:
+            raise ValueError(
+                f"Embedding has {embedding.shape[1]} components, but n_components={n_components}. "
+                f"Please provide an embedding with at least {n_components} components."
+            )
+        if library_key is not None:
+            _assert_key_in_adata(orig_adata, library_key, "obs")
+        embedding = _validated_matrix(embedding[:, :n_components], n_components, check_rows=library_key is None)
+
+        def embed(rows: np.ndarray | None) -> np.ndarray:
+            return embedding if rows is None else embedding[rows]
 
     adata = orig_adata if inplace else orig_adata.copy()
     if library_key is not None:
@@ -236,7 +278,7 @@ def calculate_niche_cellcharter(
                 logg.warning("Library '%s' contains no cells, skipping", lib_id)
                 continue
             lib_obs = adata.obs[rows].copy()
-            result_columns = _cluster(lib_obs, embedding[rows], n_components, random_state, device)
+            result_columns = _cluster(lib_obs, embed(rows), n_components, random_state, device)
             postprocess_niche_results(lib_obs, result_columns, mask, min_niche_size, f"lib={lib_id}_")
             if itr == 0:  # the reference's rule: only columns the first library added are filled
                 added_columns = list(set(lib_obs.columns) - set(adata.obs.columns))
@@ -245,7 +287,7 @@ def calculate_niche_cellcharter(
                     adata.obs[col] = NOT_A_NICHE
                 adata.obs.loc[lib_indices, col] = list(lib_obs[col].astype("str"))
     else:
-        result_columns = _cluster(adata.obs, embedding, n_components, random_state, device)
+        result_columns = _cluster(adata.obs, embed(None), n_components, random_state, device)
         postprocess_niche_results(adata.obs, result_columns, mask, min_niche_size, None)
     return None if inplace else adata
 
@@ -503,3 +545,202 @@ def niche_cellcharter_features(
             shells.close()
         m.close()
     return out
+
+
+# ---- stage 2 of the utag and cellcharter flavours: scanpy's default PCA -----------------------------------------------------------------
+# gr/_niche.py:1334, the sentence `_CellcharterEmbedder.get_embedding` logs when `use_rep` is None
+PROXY_PCA_MSG = (
+    "CellCharter recommends to use a dimensionality reduced embedding of the data, e.g. a scVI embedding. Since 'use_rep' is not provided, "
+    "PCA will be used as proxy - performance may be suboptimal."
+)
+
+
+class PCAResult(NamedTuple):
+    """What ``niche_pca`` returns: scanpy's ``obsm["X_pca"]`` (float64 here), ``varm["PCs"].T``, ``uns["pca"]["variance"]`` and
+    ``["variance_ratio"]`` — sklearn's ``fit_transform(X)``, ``components_``, ``explained_variance_``, ``explained_variance_ratio_`` — and
+    ``mean_``."""
+
+    X_pca: np.ndarray
+    components: np.ndarray
+    explained_variance: np.ndarray
+    explained_variance_ratio: np.ndarray
+    mean: np.ndarray
+
+
+def _check_aggregation(aggregation: Any) -> None:
+    if aggregation not in ("mean", "variance"):
+        raise ValueError(f"Invalid aggregation method '{aggregation}'. Please choose either 'mean' or 'variance'.")
+
+
+def pca_n_comps(n: int, d: int, n_comps: int | None = None) -> int:
+    """The number of components: ``n_comps``, or scanpy's documented default — 50, or ``min(n, d) - 1`` when ``min(n, d) <= 50``."""
+    if n_comps is None:
+        return 50 if min(n, d) > 50 else min(n, d) - 1
+    if isinstance(n_comps, bool) or not isinstance(n_comps, numbers.Integral):
+        raise TypeError(f"Expected `n_comps` to be of type `int`, found `{type(n_comps).__name__}`.")
+    if n_comps < 1:
+        raise ValueError(f"Expected `n_comps` to be positive, found `{n_comps}`.")
+    return int(n_comps)
+
+
+def _check_pca_shape(n: int, d: int, n_comps: int | None) -> int:
+    """Every refusal of the PCA kernels' limits, on the host; returns the number of components."""
+    if not (2 <= d <= PCA_MAX_FEATURES) or not (2 <= n < 2**31):
+        raise NotImplementedError(
+            f"The PCA kernels support 2 to {PCA_MAX_FEATURES} features and 2 to 2**31 - 1 rows; found {d} features and {n} rows."
+        )
+    c = pca_n_comps(n, d, n_comps)
+    if c > PCA_MAX_COMPONENTS or c >= min(n, d):
+        raise NotImplementedError(
+            f"The PCA kernels support at most {PCA_MAX_COMPONENTS} components, fewer than min(n_obs, n_features) = {min(n, d)} "
+            f"(the arpack solver's own condition); found {c}."
+        )
+    return c
+
+
+def pca_components(scatter: np.ndarray, n: int, c: int) -> tuple[np.ndarray, np.ndarray]:
+    """``(components (c, D), explained_variance (c,))`` from the centred scatter matrix of ``n`` rows: the ``c`` largest eigenpairs of
+    ``scatter / (n - 1)`` (LAPACK, on the host), descending, negative eigenvalues clamped to 0, every component oriented by sklearn's
+    ``svd_flip(u_based_decision=False)``: its entry of largest magnitude — the first one on ties — is positive."""
+    from scipy.linalg import eigh
+
+    d = scatter.shape[0]
+    lam, vec = eigh(scatter / (n - 1), subset_by_index=[d - c, d - 1])
+    lam, vec = lam[::-1], vec[:, ::-1]
+    components = np.ascontiguousarray(vec.T)
+    pivot = np.argmax(np.abs(components), axis=1)  # the first maximum
+    signs = np.sign(components[np.arange(c), pivot])
+    signs[signs == 0] = 1.0
+    components *= signs[:, None]
+    return components, np.maximum(lam, 0.0)
+
+
+def _pca_on_device(pca: DevicePCA, c: int) -> PCAResult:
+    mean, scatter = pca.moments()
+    components, variance = pca_components(scatter, pca.n, c)
+    total = np.trace(scatter) / (pca.n - 1)
+    return PCAResult(pca.project(components), components, variance, variance / total, mean)
+
+
+def niche_pca(X: Any, n_comps: int | None = None, *, device: int | None = None) -> PCAResult:
+    """scanpy's default ``sc.tl.pca`` on a dense matrix — ``sklearn.decomposition.PCA(n_comps, svd_solver="arpack",
+    random_state=0).fit_transform(X)`` — split between device and host: the column means, the centred scatter matrix
+    ``sum_i (x_i - mean)(x_i - mean)^T`` and the projection run on the GPU in float64 (``csrc/sqgr_pca.hip``); the ``c`` largest
+    eigenpairs of the D x D matrix ``scatter / (n - 1)`` come from ``scipy.linalg.eigh`` on the host, are sorted descending, clamped at
+    0 and oriented by sklearn's sign rule (in each component the entry of largest magnitude, the first on ties, is positive).
+
+    ``n_comps=None`` follows scanpy's documented rule: 50, or ``min(n, D) - 1`` when ``min(n, D) <= 50``.  Supported are
+    ``2 <= D <= 4096``, ``2 <= n < 2**31`` and ``1 <= n_comps <= 64`` with ``n_comps < min(n, D)`` (``NotImplementedError`` beyond);
+    NaN or infinity is a ``ValueError``.
+
+    The result is float64 (a float32 ``X`` is widened exactly first).  scanpy rounds ``X_pca`` to float32 by default, and sklearn's
+    mixture would then fit in float32; as with ``gmm_fit`` this library stays in float64 and is pinned to sklearn on float64 input.
+    An eigenvector is determined up to ``eps * lambda_1 / gap`` (``gap`` its eigenvalue's distance to the nearest other one): that is
+    how closely the scores follow sklearn's.  Every order of summation depends on ``(n, D)`` alone: two calls return
+    the same bytes.  Under a process group every rank computes the whole result."""
+    X = np.asarray(X)
+    if X.ndim != 2:
+        raise ValueError(f"Expected a 2-D array, found shape `{X.shape}`.")
+    n, d = X.shape
+    c = _check_pca_shape(n, d, n_comps)
+    if X.dtype not in (np.float32, np.float64):
+        X = X.astype(np.float64)
+    if X.strides[1] != X.itemsize or X.strides[0] % X.itemsize or X.strides[0] < d * X.itemsize:
+        X = np.ascontiguousarray(X)
+    if not np.isfinite(X).all():
+        raise ValueError("Input X contains NaN or infinity.")
+    ctx = default_context(device)
+    pca = _device_pca(ctx, n, d)
+    try:
+        pca.upload(X)
+        return _pca_on_device(pca, c)
+    finally:
+        pca.close()
+
+
+def _device_pca(ctx: Any, n: int, d: int) -> DevicePCA:
+    try:
+        return DevicePCA(ctx, n, d)
+    except SqgrError as exc:
+        if exc.status == -4:  # SQGR_ERR_UNSUPPORTED
+            raise NotImplementedError(str(exc)) from None
+        raise
+
+
+def _cellcharter_pca(adj: Any, X: Any, distance: int, aggregation: str, n_comps: int | None, device: int | None) -> PCAResult:
+    """``niche_pca`` of the CellCharter feature matrix of the unit graph ``adj`` (canonical CSR) and ``X``, block by block on the device."""
+    n, nv = X.shape
+    c = _check_pca_shape(n, (distance + 1) * nv, n_comps)
+    ctx = default_context(device)
+    g = cached_graph(ctx, adj, with_data=False)
+    m = DeviceMatrix(ctx, X)
+    shells = pca = None
+    try:
+        try:
+            shells = HopShells(ctx, g, distance)
+        except SqgrError as exc:
+            if exc.status == -4:  # SQGR_ERR_UNSUPPORTED
+                raise NotImplementedError(str(exc)) from None
+            raise
+        pca = _device_pca(ctx, n, (distance + 1) * nv)
+        for k in range(distance + 1):
+            pca.fill_aggregate(k * nv, m, shells=shells, k=k, variance=aggregation == "variance")
+        return _pca_on_device(pca, c)
+    finally:
+        if pca is not None:
+            pca.close()
+        if shells is not None:
+            shells.close()
+        m.close()
+
+
+def niche_cellcharter_embedding(
+    adata: Any,
+    distance: int = 3,
+    aggregation: str = "mean",
+    spatial_connectivities_key: str = "spatial_connectivities",
+    n_comps: int | None = None,
+    *,
+    table_key: str | None = None,
+    device: int | None = None,
+) -> np.ndarray:
+    """The embedding of the reference's ``cellcharter`` flavour with ``use_rep=None`` (gr/_niche.py:1336-1359):
+    ``niche_pca(niche_cellcharter_features(adata, distance, aggregation, ...), n_comps).X_pca``, bit for bit, with the
+    ``(n_obs, (distance + 1) * n_vars)`` feature matrix built and reduced on the device — only the ``(n_obs, n_comps)`` float64
+    embedding crosses to the host.  Arguments, refusals and arithmetic are those of ``niche_cellcharter_features`` and ``niche_pca``."""
+    adata = extract_adata_if_sdata(adata, table_key=table_key)
+    distance = _check_distance(distance)
+    _check_aggregation(aggregation)
+    adj = _unit_graph(adata, spatial_connectivities_key)
+    X = _feature_matrix(adata)
+    return _cellcharter_pca(adj, X, distance, aggregation, n_comps, device).X_pca
+
+
+def niche_utag_embedding(
+    adata: Any,
+    spatial_connectivities_key: str = "spatial_connectivities",
+    n_comps: int | None = None,
+    *,
+    table_key: str | None = None,
+    device: int | None = None,
+) -> np.ndarray:
+    """The embedding of the reference's ``utag`` flavour (gr/_niche.py:1259-1263): ``niche_pca(niche_utag_features(adata, ...),
+    n_comps).X_pca``, bit for bit, with the feature matrix built and reduced on the device — only the ``(n_obs, n_comps)`` float64
+    embedding crosses to the host.  The reference's next steps are ``sc.pp.neighbors`` and ``sc.tl.leiden``."""
+    adata = extract_adata_if_sdata(adata, table_key=table_key)
+    adj = _canonical_graph(adata, spatial_connectivities_key)
+    X = _feature_matrix(adata)
+    n, nv = X.shape
+    c = _check_pca_shape(n, nv, n_comps)
+    ctx = default_context(device)
+    g = cached_graph(ctx, adj, with_data=True)
+    m = DeviceMatrix(ctx, X)
+    pca = None
+    try:
+        pca = _device_pca(ctx, n, nv)
+        pca.fill_aggregate(0, m, graph=g)
+        return _pca_on_device(pca, c).X_pca
+    finally:
+        if pca is not None:
+            pca.close()
+        m.close()
