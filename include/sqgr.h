@@ -507,6 +507,31 @@ int sqgr_pca_moments(sqgr_pca* h, double* out_mean, double* out_scatter);
 int sqgr_pca_project(sqgr_pca* h, const double* components, int32_t c, double* out);
 int sqgr_pca_destroy(sqgr_pca* h);
 
+/* ---- exact kNN in feature space and UMAP's fuzzy kNN weights: the parts of `sc.pp.neighbors(adata, n_neighbors, use_rep="X")` that
+ * grow with n (gr/_niche.py:1417, in front of `sc.tl.leiden`).  Float64 throughout, no float atomics, no FMA.
+ *
+ * sqgr_knn_nd_info: out_info int64[4] = {query rows of a block, candidate rows of a tile, largest D, largest k}.  Needs no device.
+ * sqgr_knn_nd: x a HOST row-major matrix of n rows and D columns, ld values apart, of value_bytes 8 (float64) or 4 (float32, widened
+ *   exactly).  For every row its k nearest OTHER rows (self excluded by index), ascending by (d2, index): ties go to the smaller
+ *   index.  out_idx int32[n][k], out_d2 float64[n][k] (HOST), out_d2[i][r] = sum_j (x[i][j] - x[c][j])^2 with j ascending and every
+ *   difference, product and sum rounded on its own — sklearn's KD-tree `rdist`; the caller takes the square root.  All pairs are
+ *   computed (3 D float64 operations per ordered pair).  The result does not depend on the launch geometry; two calls return the
+ *   same bytes.  SQGR_ERR_UNSUPPORTED unless 1 <= D <= 256, 1 <= k <= min(64, n - 1) and n < 2^31.
+ * sqgr_fuzzy_knn: UMAP's `smooth_knn_dist` and `compute_membership_strengths` for local_connectivity = 1, one lane per row.
+ *   dist float64[n][k] (HOST): the true distances of a row's k neighbours, ascending; the row's own zero is the implicit column 0 of
+ *   scanpy's m = k + 1 neighbours.  rho_i = the first dist[i][j] > 0, else 0.  sigma_i: bisection from lo = 0, hi = inf, mid = 1, at
+ *   most 64 sweeps of psum = sum_j (dist[i][j] - rho_i > 0 ? exp(-((dist[i][j] - rho_i) / mid)) : 1), j ascending, until
+ *   |psum - log2(m)| < 1e-5; psum > log2(m): hi = mid, mid = (lo + hi) / 2; else lo = mid, mid = hi == inf ? 2 mid : (lo + hi) / 2.
+ *   Then sigma_i = max(sigma_i, 1e-3 * (sum_j dist[i][j], ascending) / m) when rho_i > 0, else max(sigma_i, 1e-3 * mean_all), with
+ *   mean_all = dist.sum() / (n m) from the caller.  out_iters[i] int32: the index of the last sweep, 0 .. 63.  out_vals
+ *   float64[n][k] = (dist[i][j] - rho_i <= 0 or sigma_i == 0) ? 1 : exp(-((dist[i][j] - rho_i) / sigma_i)).
+ *   SQGR_ERR_UNSUPPORTED unless 1 <= k <= 64 and n < 2^31. */
+int sqgr_knn_nd_info(int64_t* out_info);
+int sqgr_knn_nd(sqgr_ctx* ctx, const void* x, int32_t value_bytes, int64_t n, int32_t D, int64_t ld, int32_t k, int32_t* out_idx,
+                double* out_d2);
+int sqgr_fuzzy_knn(sqgr_ctx* ctx, const double* dist, int64_t n, int32_t k, double mean_all, double* out_rho, double* out_sigma,
+                   int32_t* out_iters, double* out_vals);
+
 #ifdef __cplusplus
 }
 #endif

@@ -126,6 +126,9 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "sqgr_pca_moments": (C.c_int, [C.c_void_p, c_f64p, c_f64p]),
     "sqgr_pca_project": (C.c_int, [C.c_void_p, c_f64p, C.c_int32, c_f64p]),
     "sqgr_pca_destroy": (C.c_int, [C.c_void_p]),
+    "sqgr_knn_nd_info": (C.c_int, [c_i64p]),
+    "sqgr_knn_nd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int32, c_i32p, c_f64p]),
+    "sqgr_fuzzy_knn": (C.c_int, [C.c_void_p, c_f64p, C.c_int64, C.c_int32, C.c_double, c_f64p, c_f64p, c_i32p, c_f64p]),
 }
 
 
@@ -970,6 +973,40 @@ class DevicePCA:
             self.close()
         except Exception:
             pass
+
+
+def knn_nd_info() -> dict[str, int]:
+    """Constants of ``csrc/sqgr_knn_nd.hip`` (``sqgr_knn_nd_info``); needs the library, not a device."""
+    lib = load_library()
+    out = np.zeros(4, dtype=np.int64)
+    _check(lib, lib.sqgr_knn_nd_info(_ptr(out, c_i64p)))
+    return {"query_rows": int(out[0]), "tile_rows": int(out[1]), "max_features": int(out[2]), "max_neighbors": int(out[3])}
+
+
+def knn_nd(ctx: Context, x: np.ndarray, k: int) -> tuple[np.ndarray, np.ndarray]:
+    """``sqgr_knn_nd``: ``(indices int32 (n, k), d2 float64 (n, k))`` of the ``k`` nearest other rows of every row of ``x`` (float64 or
+    float32, unit stride along a row), ascending by ``(d2, index)``."""
+    assert x.ndim == 2 and x.dtype in (np.float32, np.float64) and (x.shape[1] == 0 or x.strides[1] == x.itemsize), (x.dtype, x.strides)
+    n, d = x.shape
+    k = int(k)
+    idx = np.empty((n, max(k, 0)), dtype=np.int32)
+    d2 = np.empty((n, max(k, 0)), dtype=np.float64)
+    ld = max(x.strides[0] // x.itemsize, d) if n > 1 else d
+    _check(ctx.lib, ctx.lib.sqgr_knn_nd(ctx.h, C.c_void_p(x.ctypes.data), x.itemsize, n, d, ld, k, _ptr(idx, c_i32p), _ptr(d2, c_f64p)))
+    return idx, d2
+
+
+def fuzzy_knn(ctx: Context, dist: np.ndarray, mean_all: float) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """``sqgr_fuzzy_knn``: ``(rho (n,), sigma (n,), iters int32 (n,), vals (n, k))`` of the ascending true distances ``dist (n, k)``."""
+    dist = _as(dist, np.float64)
+    n, k = dist.shape
+    rho = np.empty(n, dtype=np.float64)
+    sigma = np.empty(n, dtype=np.float64)
+    iters = np.empty(n, dtype=np.int32)
+    vals = np.empty((n, k), dtype=np.float64)
+    _check(ctx.lib, ctx.lib.sqgr_fuzzy_knn(ctx.h, _ptr(dist, c_f64p), n, k, float(mean_all), _ptr(rho, c_f64p), _ptr(sigma, c_f64p),
+                                           _ptr(iters, c_i32p), _ptr(vals, c_f64p)))
+    return rho, sigma, iters, vals
 
 
 class AutocorrPlan:
