@@ -532,6 +532,44 @@ int sqgr_knn_nd(sqgr_ctx* ctx, const void* x, int32_t value_bytes, int64_t n, in
 int sqgr_fuzzy_knn(sqgr_ctx* ctx, const double* dist, int64_t n, int32_t k, double mean_all, double* out_rho, double* out_sigma,
                    int32_t* out_iters, double* out_vals);
 
+/* ---- Leiden communities of a symmetric weighted graph: `sc.tl.leiden(adata, resolution)` of the `neighborhood` and `utag` flavours
+ * (gr/_niche.py:1428; leidenalg's RBConfigurationVertexPartition, Q = sum_c (in_c / 2m - gamma (tot_c / 2m)^2)) as a deterministic
+ * synchronous variant on exact integers.  leidenalg itself is randomised; parity with it is not claimed.
+ *
+ * sqgr_leiden_info: out_info int64[6] = {weight scale bits (the caller quantises q = max(1, rint(w / w_max * 2^24)), int32), sweep cap
+ *   of one local moving or refinement phase, iteration cap for n_iterations < 0, on-chip capacity: the stored entries of a row up to
+ *   which its neighbour communities are tabulated in LDS (longer rows take the global-memory path), slots of that table, entries of
+ *   out_stats}.  Needs no device.
+ * sqgr_leiden: HOST arrays in canonical CSR: indptr int64[n + 1], indices int32[nnz] strictly increasing in a row, no self loop, every
+ *   entry mirrored with an equal weight, weights int32[nnz] >= 1 — checked on the device, SQGR_ERR_INVALID names the property that
+ *   failed.  resolution finite and > 0; n_iterations > 0, or < 0 for "until an iteration changes nothing" (at most the iteration cap).
+ *   SQGR_ERR_UNSUPPORTED when the sum of all weights 2m reaches 2^62 or n >= 2^31 - 1.
+ *   Arithmetic: every k_v, k_{v,c}, tot_c, in_c and 2m is an exact int64 on every level.  The one floating-point expression is
+ *     gain(v, c) = (double)k_vc - gamma * (double)k_v * (double)(tot_c - [c == comm(v)] k_v) / (double)two_m
+ *   evaluated left to right, every operation rounded on its own.  Candidates: (gain descending, community id ascending); a move needs
+ *   gain(v, c) > gain(v, comm(v)) strictly; a self loop of a coarse node counts in k_v, not in k_vc.
+ *   Per iteration and level: (1) local moving in synchronous sweeps s = 0, 1, ..: every vertex picks its best target among its
+ *   neighbours' communities on the state the sweep began with; of the vertices that want to move, one moves when
+ *   (hash(vertex, s), vertex) is smaller than that of every neighbour that wants to move too, hash(v, s): x = v * 0x9E3779B1 + s *
+ *   0x85EBCA77; x ^= x >> 16; x *= 0x7FEB352D; x ^= x >> 15; x *= 0x846CA68B; x ^= x >> 16 (uint32).  Against overshoot, of all the
+ *   vertices that want into one community c (W_c the sum of their k) the one of smallest (hash, vertex) is exempt; any other moves
+ *   only if (double)k_vc - gamma * (double)k_v * (double)(tot_c + W_c - k_v) / two_m > gain(v, comm(v)).  Ends at a sweep without a move,
+ *   or after the sweep cap with the assignment of largest Q among the start and every sweep (the first such), Q = (double)sum_in /
+ *   (double)two_m - gamma * ((double)sum_c tot_c^2 / ((double)two_m * (double)two_m)) from the exact integers.  (2) Refinement from
+ *   singletons, the same sweeps with targets inside the vertex's community: only a vertex still alone moves, and only when
+ *   (double)k_{v, C - v} >= gamma * (double)k_v * (double)(tot_C - k_v) / two_m; a target S needs the same of k_{S, C - S} and tot_S;
+ *   gain(v, S) = k_vS - gamma k_v tot_S / 2m must be > 0.  (3) Aggregation: refined communities numbered ascending by their id
+ *   become nodes, parallel edges summed, inner weight on a self loop; a node starts in the community of its members.  The levels
+ *   end when local moving leaves every node alone or refinement merges nothing; the last level's nodes are the communities.  An
+ *   iteration starts at the input graph from the previous labels.
+ *   out_labels int32[n] in [0, K): communities numbered by size descending, ties by smallest member.  out_stats int64[8] = {K,
+ *   iterations run, levels, sweeps, sum_c in_c of the result, 2m, local moving phases that ended at the sweep cap, 1 when the last
+ *   iteration changed nothing}.  A graph without entries: every vertex alone, all other stats 0.
+ *   The result does not depend on the launch geometry; two calls return the same bytes. */
+int sqgr_leiden_info(int64_t* out_info);
+int sqgr_leiden(sqgr_ctx* ctx, int64_t n, const int64_t* indptr, const int32_t* indices, const int32_t* weights, double resolution,
+                int32_t n_iterations, int32_t* out_labels, int64_t* out_stats);
+
 #ifdef __cplusplus
 }
 #endif

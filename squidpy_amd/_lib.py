@@ -129,6 +129,8 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "sqgr_knn_nd_info": (C.c_int, [c_i64p]),
     "sqgr_knn_nd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int32, c_i32p, c_f64p]),
     "sqgr_fuzzy_knn": (C.c_int, [C.c_void_p, c_f64p, C.c_int64, C.c_int32, C.c_double, c_f64p, c_f64p, c_i32p, c_f64p]),
+    "sqgr_leiden_info": (C.c_int, [c_i64p]),
+    "sqgr_leiden": (C.c_int, [C.c_void_p, C.c_int64, c_i64p, c_i32p, c_i32p, C.c_double, C.c_int32, c_i32p, c_i64p]),
 }
 
 
@@ -1007,6 +1009,35 @@ def fuzzy_knn(ctx: Context, dist: np.ndarray, mean_all: float) -> tuple[np.ndarr
     _check(ctx.lib, ctx.lib.sqgr_fuzzy_knn(ctx.h, _ptr(dist, c_f64p), n, k, float(mean_all), _ptr(rho, c_f64p), _ptr(sigma, c_f64p),
                                            _ptr(iters, c_i32p), _ptr(vals, c_f64p)))
     return rho, sigma, iters, vals
+
+
+LEIDEN_STATS = ("n_communities", "iterations", "levels", "sweeps", "sum_in", "two_m", "cap_hits", "settled")
+
+
+def leiden_info() -> dict[str, int]:
+    """Constants of ``csrc/sqgr_leiden.hip`` (``sqgr_leiden_info``); needs the library, not a device."""
+    lib = load_library()
+    out = np.zeros(6, dtype=np.int64)
+    _check(lib, lib.sqgr_leiden_info(_ptr(out, c_i64p)))
+    return {"weight_bits": int(out[0]), "sweep_cap": int(out[1]), "iteration_cap": int(out[2]), "capacity": int(out[3]),
+            "table_slots": int(out[4]), "n_stats": int(out[5])}
+
+
+def leiden(ctx: Context, indptr: np.ndarray, indices: np.ndarray, weights: np.ndarray, resolution: float,
+           n_iterations: int = -1) -> tuple[np.ndarray, dict[str, int]]:
+    """``sqgr_leiden``: ``(labels int32 (n,), stats)`` of a canonical symmetric CSR graph with int32 weights >= 1; ``stats`` has the
+    keys of ``LEIDEN_STATS``."""
+    indptr = _as(indptr, np.int64)
+    indices = _as(indices, np.int32)
+    weights = _as(weights, np.int32)
+    n = indptr.shape[0] - 1
+    assert n >= 1 and indices.shape == weights.shape and indices.ndim == 1, (n, indices.shape, weights.shape)
+    assert indptr[-1] == indices.shape[0], (indptr[-1], indices.shape)
+    labels = np.empty(n, dtype=np.int32)
+    stats = np.zeros(len(LEIDEN_STATS), dtype=np.int64)
+    _check(ctx.lib, ctx.lib.sqgr_leiden(ctx.h, n, _ptr(indptr, c_i64p), _ptr(indices, c_i32p), _ptr(weights, c_i32p), float(resolution),
+                                        int(n_iterations), _ptr(labels, c_i32p), _ptr(stats, c_i64p)))
+    return labels, dict(zip(LEIDEN_STATS, (int(s) for s in stats)))
 
 
 class AutocorrPlan:

@@ -268,6 +268,18 @@ def calculate_niche_cellcharter(
         def embed(rows: np.ndarray | None) -> np.ndarray:
             return embedding if rows is None else embedding[rows]
 
+    def cluster(adata: Any, obs: pd.DataFrame, rows: np.ndarray | None) -> list[str]:
+        return _cluster(obs, embed(rows), n_components, random_state, device)
+
+    return calculate_niche_custom(orig_adata, cluster, min_niche_size, mask, library_key, inplace)
+
+
+def calculate_niche_custom(orig_adata: Any, cluster: Any, min_niche_size: int | None, mask: pd.Series | None, library_key: str | None,
+                           inplace: bool) -> Any:
+    """The frame of ``_calculate_niche_custom`` (gr/_niche.py:200-271) every flavour shares.  ``cluster(adata, obs, rows)`` computes the
+    niche columns of the observations ``rows`` (a boolean mask over ``adata``, ``None`` for all), writes them into ``obs`` and returns
+    their names.  With ``library_key`` every library is clustered on its own, in ``obs[library_key].unique()`` order, and its labels
+    are prefixed ``lib={id}_``; only columns the first library added are filled (the reference's rule)."""
     adata = orig_adata if inplace else orig_adata.copy()
     if library_key is not None:
         logg.info("Stratifying by library_key '%s'", library_key)
@@ -278,7 +290,7 @@ def calculate_niche_cellcharter(
                 logg.warning("Library '%s' contains no cells, skipping", lib_id)
                 continue
             lib_obs = adata.obs[rows].copy()
-            result_columns = _cluster(lib_obs, embed(rows), n_components, random_state, device)
+            result_columns = cluster(adata, lib_obs, rows)
             postprocess_niche_results(lib_obs, result_columns, mask, min_niche_size, f"lib={lib_id}_")
             if itr == 0:  # the reference's rule: only columns the first library added are filled
                 added_columns = list(set(lib_obs.columns) - set(adata.obs.columns))
@@ -287,7 +299,7 @@ def calculate_niche_cellcharter(
                     adata.obs[col] = NOT_A_NICHE
                 adata.obs.loc[lib_indices, col] = list(lib_obs[col].astype("str"))
     else:
-        result_columns = _cluster(adata.obs, embed(None), n_components, random_state, device)
+        result_columns = cluster(adata, adata.obs, None)
         postprocess_niche_results(adata.obs, result_columns, mask, min_niche_size, None)
     return None if inplace else adata
 
