@@ -570,6 +570,46 @@ int sqgr_leiden_info(int64_t* out_info);
 int sqgr_leiden(sqgr_ctx* ctx, int64_t n, const int64_t* indptr, const int32_t* indices, const int32_t* weights, double resolution,
                 int32_t n_iterations, int32_t* out_labels, int64_t* out_stats);
 
+/* ---- Multiplex Leiden on two layers over the same vertices: what `calculate_niche_spatialleiden` (gr/_niche.py:466-620) gets from
+ * spatialleiden, i.e. leidenalg's optimise_partition_multiplex over one RBConfigurationVertexPartition per layer with layer_weights
+ * [1, layer_ratio].  Layer 0 is the latent graph, layer 1 the spatial graph.  The objective is unnormalised,
+ *     Q = sum_l a_l sum_c (in^l_c - gamma_l (tot^l_c)^2 / 2m_l),  a_0 = 1, a_1 = layer_ratio,
+ * so a layer counts in proportion to its total weight; the caller quantises both layers with ONE common scale.  Parity with
+ * spatialleiden / leidenalg is not claimed.  The contract is sqgr_leiden's with the changes below and nothing else.
+ *
+ * sqgr_leiden_multiplex_info: out_info int64[7] = the six entries of sqgr_leiden_info (entries of out_stats: 10), then the number of
+ *   layers (2).  Needs no device.
+ * sqgr_leiden_multiplex: per layer l HOST arrays as for sqgr_leiden (canonical symmetric CSR, no self loop, int32 weights >= 1); a
+ *   layer may be empty (indptr all zero; indices / weights may then be null).  Checked on the device; SQGR_ERR_INVALID names the layer
+ *   ("layer 0" / "layer 1") and the property that failed.  resolution0, resolution1 and layer_ratio finite and > 0; n_iterations as for
+ *   sqgr_leiden.  SQGR_ERR_UNSUPPORTED when either 2m_l reaches 2^62 or n >= 2^31 - 1.
+ *   Integers: every k^l_v, k^l_{v,c}, tot^l_c, in^l_c, 2m_l and W^l_c is an exact int64, per layer and on every level.
+ *   Gain: per layer g_l(v, c) = (double)k^l_vc - gamma_l * (double)k^l_v * (double)(tot^l_c - [c == comm(v)] k^l_v) / (double)two_m_l,
+ *   left to right, every operation rounded on its own; g_l is exactly +0.0 for a layer with 2m_l = 0.  gain(v, c) = g_0 + layer_ratio *
+ *   g_1: the product is rounded, then the sum, no FMA.  Every floating-point test below mixes its two per-layer terms t_0, t_1 the same
+ *   way, t_0 + layer_ratio * t_1, a term being +0.0 for a layer with 2m_l = 0.
+ *   Candidates: the communities of v's neighbours in either layer, plus its own; one candidate per community (its k^0_vc and k^1_vc
+ *   belong to the same candidate).  Order (gain descending, community id ascending) and the strict-improvement rule as in sqgr_leiden.
+ *   Independent set: a vertex that wants to move yields to a neighbour IN EITHER LAYER that wants to move too and has the smaller
+ *   (hash(vertex, s), vertex).  Overshoot rule: W^l_c, the sum of k^l_v over the vertices that want into c, is kept per layer; a vertex
+ *   that is not the first of them moves only if t_l = (double)k^l_vc - gamma_l * (double)k^l_v * (double)(tot^l_c + W^l_c - k^l_v) /
+ *   two_m_l mixed as above is > gain(v, comm(v)).
+ *   Quality at the sweep cap: Q = (double)two_m_0 * q_0 + layer_ratio * ((double)two_m_1 * q_1), q_l the single-layer expression of
+ *   sqgr_leiden formed from layer l's exact integers, 0 for a layer with 2m_l = 0.
+ *   Refinement: a vertex is well connected when (x_0 - p_0) + layer_ratio * (x_1 - p_1) >= 0 with x_l = (double)k^l_{v, C - v} and p_l =
+ *   gamma_l * (double)k^l_v * (double)(tot^l_C - k^l_v) / two_m_l; a target S needs the same of k^l_{S, C - S} and tot^l_S; S must be
+ *   adjacent to v in at least one layer and gain(v, S) (g_l = k^l_vS - gamma_l k^l_v tot^l_S / 2m_l) must be > 0.
+ *   Aggregation: one coarse CSR per layer over the same numbering of the refined communities; the self loop of a coarse node in
+ *   layer l carries in^l_c.  Levels, iterations and the canonical labelling as in sqgr_leiden.
+ *   out_labels int32[n]; out_stats int64[10] = {K, iterations run, levels, sweeps, sum_c in^0_c, 2m_0, sum_c in^1_c, 2m_1, local moving
+ *   phases that ended at the sweep cap, 1 when the last iteration changed nothing}.  Both layers empty: every vertex alone, all other
+ *   stats 0.  On-chip path: a row whose stored entries in layer 0 plus those in layer 1 are <= the capacity; otherwise the
+ *   global-memory path.  The result does not depend on the path or the launch geometry; two calls return the same bytes. */
+int sqgr_leiden_multiplex_info(int64_t* out_info);
+int sqgr_leiden_multiplex(sqgr_ctx* ctx, int64_t n, const int64_t* indptr0, const int32_t* indices0, const int32_t* weights0,
+                          const int64_t* indptr1, const int32_t* indices1, const int32_t* weights1, double resolution0, double resolution1,
+                          double layer_ratio, int32_t n_iterations, int32_t* out_labels, int64_t* out_stats);
+
 #ifdef __cplusplus
 }
 #endif

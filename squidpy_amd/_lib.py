@@ -131,6 +131,9 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "sqgr_fuzzy_knn": (C.c_int, [C.c_void_p, c_f64p, C.c_int64, C.c_int32, C.c_double, c_f64p, c_f64p, c_i32p, c_f64p]),
     "sqgr_leiden_info": (C.c_int, [c_i64p]),
     "sqgr_leiden": (C.c_int, [C.c_void_p, C.c_int64, c_i64p, c_i32p, c_i32p, C.c_double, C.c_int32, c_i32p, c_i64p]),
+    "sqgr_leiden_multiplex_info": (C.c_int, [c_i64p]),
+    "sqgr_leiden_multiplex": (C.c_int, [C.c_void_p, C.c_int64, c_i64p, c_i32p, c_i32p, c_i64p, c_i32p, c_i32p, C.c_double, C.c_double, C.c_double,
+                                        C.c_int32, c_i32p, c_i64p]),
 }
 
 
@@ -1038,6 +1041,37 @@ def leiden(ctx: Context, indptr: np.ndarray, indices: np.ndarray, weights: np.nd
     _check(ctx.lib, ctx.lib.sqgr_leiden(ctx.h, n, _ptr(indptr, c_i64p), _ptr(indices, c_i32p), _ptr(weights, c_i32p), float(resolution),
                                         int(n_iterations), _ptr(labels, c_i32p), _ptr(stats, c_i64p)))
     return labels, dict(zip(LEIDEN_STATS, (int(s) for s in stats)))
+
+
+MULTIPLEX_STATS = ("n_communities", "iterations", "levels", "sweeps", "sum_in_0", "two_m_0", "sum_in_1", "two_m_1", "cap_hits", "settled")
+
+
+def leiden_multiplex_info() -> dict[str, int]:
+    """Constants of ``csrc/sqgr_leiden_multiplex.hip`` (``sqgr_leiden_multiplex_info``); needs the library, not a device."""
+    lib = load_library()
+    out = np.zeros(7, dtype=np.int64)
+    _check(lib, lib.sqgr_leiden_multiplex_info(_ptr(out, c_i64p)))
+    return {"weight_bits": int(out[0]), "sweep_cap": int(out[1]), "iteration_cap": int(out[2]), "capacity": int(out[3]),
+            "table_slots": int(out[4]), "n_stats": int(out[5]), "n_layers": int(out[6])}
+
+
+def leiden_multiplex(ctx: Context, layer0: tuple, layer1: tuple, resolutions: tuple[float, float] = (1.0, 1.0), layer_ratio: float = 1.0,
+                     n_iterations: int = -1) -> tuple[np.ndarray, dict[str, int]]:
+    """``sqgr_leiden_multiplex``: ``(labels int32 (n,), stats)`` of two ``(indptr, indices, weights)`` layers over the same vertices,
+    each a canonical symmetric CSR graph with int32 weights >= 1 (a layer may be empty); ``stats`` has the keys of ``MULTIPLEX_STATS``."""
+    args = []
+    n = np.asarray(layer0[0]).shape[0] - 1
+    for indptr, indices, weights in (layer0, layer1):
+        indptr, indices, weights = _as(indptr, np.int64), _as(indices, np.int32), _as(weights, np.int32)
+        assert indptr.shape == (n + 1,) and n >= 1 and indices.shape == weights.shape and indices.ndim == 1, (n, indptr.shape, indices.shape)
+        assert indptr[-1] == indices.shape[0], (indptr[-1], indices.shape)
+        args += [indptr, indices, weights]
+    labels = np.empty(n, dtype=np.int32)
+    stats = np.zeros(len(MULTIPLEX_STATS), dtype=np.int64)
+    ptrs = [_ptr(a, c_i64p if i % 3 == 0 else c_i32p) for i, a in enumerate(args)]
+    _check(ctx.lib, ctx.lib.sqgr_leiden_multiplex(ctx.h, n, *ptrs, float(resolutions[0]), float(resolutions[1]), float(layer_ratio),
+                                                  int(n_iterations), _ptr(labels, c_i32p), _ptr(stats, c_i64p)))
+    return labels, dict(zip(MULTIPLEX_STATS, (int(s) for s in stats)))
 
 
 class AutocorrPlan:

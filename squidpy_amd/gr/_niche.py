@@ -275,11 +275,12 @@ def calculate_niche_cellcharter(
 
 
 def calculate_niche_custom(orig_adata: Any, cluster: Any, min_niche_size: int | None, mask: pd.Series | None, library_key: str | None,
-                           inplace: bool) -> Any:
+                           inplace: bool, prefix: str | None = None) -> Any:
     """The frame of ``_calculate_niche_custom`` (gr/_niche.py:200-271) every flavour shares.  ``cluster(adata, obs, rows)`` computes the
     niche columns of the observations ``rows`` (a boolean mask over ``adata``, ``None`` for all), writes them into ``obs`` and returns
     their names.  With ``library_key`` every library is clustered on its own, in ``obs[library_key].unique()`` order, and its labels
-    are prefixed ``lib={id}_``; only columns the first library added are filled (the reference's rule)."""
+    are prefixed ``lib={id}_``; only columns the first library added are filled (the reference's rule).  ``prefix`` (the spatialleiden
+    flavour's) goes in front of the labels where there is no ``library_key``, as in gr/_niche.py:571 and :610."""
     adata = orig_adata if inplace else orig_adata.copy()
     if library_key is not None:
         logg.info("Stratifying by library_key '%s'", library_key)
@@ -300,7 +301,7 @@ def calculate_niche_custom(orig_adata: Any, cluster: Any, min_niche_size: int | 
                 adata.obs.loc[lib_indices, col] = list(lib_obs[col].astype("str"))
     else:
         result_columns = cluster(adata, adata.obs, None)
-        postprocess_niche_results(adata.obs, result_columns, mask, min_niche_size, None)
+        postprocess_niche_results(adata.obs, result_columns, mask, min_niche_size, prefix)
     return None if inplace else adata
 
 
