@@ -1389,6 +1389,7 @@ int sqgr_nhood::resolve_tuning() {
 int sqgr_nhood::ensure_workspace() {
     SQGR_TRY(resolve_tuning());
     SQGR_TRY(keys.ensure(2 * keys_stride()));
+    SQGR_TRY(shuf.ensure_tab_workspace(B, nbatch));  // one set of tables: the build and its reader run back to back on one stream
     {   // the zero bytes behind the rows of either buffer (slab_stride) are written here, once per allocation, and never again
         const uint8_t* had = slab.p;
         const size_t had_n = slab.n;

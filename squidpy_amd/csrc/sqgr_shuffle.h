@@ -107,6 +107,8 @@ struct LabelShuffler {
     bool has_labels = false;
     int max_label_count = 0;    // largest cluster of the base labels (0: unknown — injected label vectors)
     const char* fix_why = nullptr;  // why these tables keep k_shuffle_tab's sentinel test (NULL: the FIX pair may run — create)
+    DevBuf<uint32_t> tab_ws;    // k_shuffle_tab's round-1 tables of a launch, [row pair][2][A][8] words (k_shuffle_tab_build)
+    size_t tab_workspace_words(int row_pairs) const { return (size_t)row_pairs * 2 * dom0.dom.A * 8; }
     bool wide() const { return K > 256; }  // 16-bit labels
     bool mapped() const { return spot_of.p != nullptr; }
 
@@ -118,6 +120,10 @@ struct LabelShuffler {
     int independent_mode(int B, bool* independent) const;
     // keys of nrows slab rows of B permutations from permutation perm0 (a multiple of 16) on; timer: LaunchTimer name or NULL
     int keygen(const char* timer, uint64_t seed, int64_t perm0, int nrows, int B, bool independent, uint32_t* keys, hipStream_t st) const;
+    // tab_ws for launches of up to nb_max batches of B permutations, where the table kernel can take them at all (16-wide rows, no
+    // libraries, at most 2^20 spots and 256 clusters; 5 MB at 1e6 spots x 160 rows).  The owner of the key and slab buffers calls
+    // it where it sizes those: launch_shuffle_raw allocates nothing
+    int ensure_tab_workspace(int B, int nb_max);
     // slab rows of nb batches of B permutations from their keys; pw: plane width of a 16-wide batch (slab_store16)
     int launch_shuffle_raw(int B, int nb, const uint32_t* keys, uint8_t* slab, hipStream_t st, bool independent, int pw = 16) const;
     // numpy streams, 16-bit labels: nb batches of base16 gathered through the permutations p0 .. of perm_idx (zeros from p_valid on)

@@ -6,8 +6,9 @@
 //   k_shuffle_tab : the same labels for 16-wide rows without libraries on up to 2^20 spots, at launch-group size: the first
 //               round of the per-permutation network depends on the spot only through the high digit of its group image, so
 //               each block tabulates it in LDS per row pair (64 KB) and a spot reads it back — 3 packed instructions per
-//               permutation pair instead of 10 (launch_shuffle_raw selects; SQGR_SHUFFLE_TABLE=0|1|2).  On tables whose only
-//               sentinel labels are the ranks >= n it runs without the sentinel test, and
+//               permutation pair instead of 10 (launch_shuffle_raw selects; SQGR_SHUFFLE_TABLE=0|1|2).  The tables of a launch's
+//               row pairs are built once, by k_shuffle_tab_build in front of it, and copied (SQGR_SHUFFLE_PRETAB=0: built by
+//               every block, as before).  On tables whose only sentinel labels are the ranks >= n it runs without the sentinel test, and
 //   k_shuffle_fix : behind it, thread per out-of-range rank and permutation, writes the labels whose first sigma image left
 //               [0, n) from the inverse networks (SQGR_SHUFFLE_FIX=0|2).
 // The numpy streams (PCG64 + Generator.shuffle) are sqgr_pcg.hip's; k_gather_labels16 applies their permutations to 16-bit labels.
@@ -267,13 +268,20 @@ __device__ __forceinline__ u16x2 shuf_tab_F2(u16x2 v, u16x2 k, u16x2 sh, u16x2 c
     x *= (u16x2)(FEISTEL_C2);
     return x >> sh;
 }
+// x + y in both 16-bit halves as ONE 32-bit add of the bit-cast words (v_add_u32 instead of v_pk_add_u16: 2.9 against 4.2 clk per
+// SIMD, profiles/r06_ubench_ops.json).  Exact iff the low halves' sum stays below 2^16 — nothing then carries into the high half;
+// every call site states its bound.  They follow from make_domain (sqgr_rng.h) for every n <= 2^27: A = 2^m, 16 <= B <= A <= 2^14,
+// Bmask + 1 = 2^ceil(log2 B) < 2B, F_A = x >> ash < A, F_B = x >> bsh <= Bmask (tests/test_shuffle_pretab_cpu.py).
+__device__ __forceinline__ u16x2 add_nocarry(u16x2 x, u16x2 y) {
+    return __builtin_bit_cast(u16x2, __builtin_bit_cast(uint32_t, x) + __builtin_bit_cast(uint32_t, y));
+}
 // feistel_rounds<1> on shuf_tab_F2
 __device__ __forceinline__ void shuf_tab_rounds(u16x2& a, u16x2& b, const uint32_t (&kp)[8], u16x2 am, u16x2 ash, u16x2 bsh, u16x2 BB,
                                                 u16x2 c1) {
 #pragma unroll
     for (int r = 0; r < FEISTEL_ROUNDS; r += 2) {
-        a = (a + shuf_tab_F2(b, __builtin_bit_cast(u16x2, kp[r]), ash, c1)) & am;
-        u16x2 t = b + shuf_tab_F2(a, __builtin_bit_cast(u16x2, kp[r + 1]), bsh, c1);
+        a = add_nocarry(a, shuf_tab_F2(b, __builtin_bit_cast(u16x2, kp[r]), ash, c1)) & am;      // a < A, F_A < A: < 2A <= 2^15
+        u16x2 t = add_nocarry(b, shuf_tab_F2(a, __builtin_bit_cast(u16x2, kp[r + 1]), bsh, c1));  // b < B, F_B < 2B: < 3B < 2^16
         t = __builtin_elementwise_min(t, (u16x2)(t - BB));
         b = __builtin_elementwise_min(t, (u16x2)(t - BB));
     }
@@ -290,6 +298,32 @@ __device__ __forceinline__ uint32_t first_label(uint32_t e, uint32_t bpk, uint32
     return word;
 }
 
+// The tables of ALL row pairs of a launch, once (k_shuffle_tab<.., PRETAB = true> copies them): tabs[y][g][a][t] for row pair y =
+// blockIdx.y, the words of the in-block build — feistel_F2 on the pair's k0 keys, one conditional subtraction — in the same order.
+// 2 * A * 8 words per row pair; an odd last row is paired with itself, as in k_shuffle_tab.
+__global__ __launch_bounds__(256) void k_shuffle_tab_build(const uint32_t* __restrict__ keys, FeistelDomain dom, int nrows,
+                                                           uint32_t* __restrict__ tabs) {
+    const int row0 = 2 * blockIdx.y;
+    const int row1 = min(row0 + 1, nrows - 1);
+    constexpr size_t row_words = key_words_per_row(16, 1);
+    const uint32_t* ksA = keys + (size_t)row0 * row_words + 8;
+    const uint32_t* ksB = keys + (size_t)row1 * row_words + 8;
+    const u16x2 BB = (u16x2)((unsigned short)dom.B);
+    const u16x2 bsh = (u16x2)((unsigned short)dom.bsh);
+    const int words = (int)dom.A * 8;
+    uint32_t* out = tabs + (size_t)blockIdx.y * 2 * words;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < words; idx += gridDim.x * 256) {
+        const u16x2 av = (u16x2)((unsigned short)(idx >> 3));
+        const int t = idx & 7;
+        u16x2 fa = feistel_F2(av, __builtin_bit_cast(u16x2, ksA[t * 2]), bsh);
+        u16x2 fb = feistel_F2(av, __builtin_bit_cast(u16x2, ksB[t * 2]), bsh);
+        fa = __builtin_elementwise_min(fa, (u16x2)(fa - BB));
+        fb = __builtin_elementwise_min(fb, (u16x2)(fb - BB));
+        out[idx] = __builtin_bit_cast(uint32_t, fa);
+        out[words + idx] = __builtin_bit_cast(uint32_t, fb);
+    }
+}
+
 // NOMAP: no spot map — the rank of slab row i is i itself, and its digits (a0, b0) advance with the grid stride instead of being
 // divided out per spot.
 // FIX (launch_shuffle_raw decides; SQGR_SHUFFLE_FIX): no sentinel test and no exact route.  The only labels that need the route
@@ -298,11 +332,15 @@ __device__ __forceinline__ uint32_t first_label(uint32_t e, uint32_t bpk, uint32
 // kernel, writes exactly those from the inverse networks.  Here the entries of the blocks that reach past rank n (the partial
 // block, which eligibility requires to end in label K - 1, and with B clamped to 16 whole blocks behind it) are replaced while
 // the table is copied into LDS by  K - 1 | 0xFFFF << 16 : every byte this kernel stores is a label < K, whatever runs later.
-template <bool SMALLK, bool NOMAP, bool FIX>
+// PRETAB (launch_shuffle_raw decides; SQGR_SHUFFLE_PRETAB): T depends on the row pair's sigma keys alone, yet every one of the
+// launch's blocks of a row pair (62 at 1e6 spots x 160 rows) built it again.  k_shuffle_tab_build, launched in front of this kernel,
+// computes the tables of all row pairs once into `tabs` — [row pair][g][a][t], the LDS image — and a block copies its 2 * A * 32
+// bytes with 16-byte loads and stores.  PRETAB = false keeps the in-block build (tabs is not read).
+template <bool SMALLK, bool NOMAP, bool FIX, bool PRETAB>
 __global__ __launch_bounds__(SHUF_TAB_THREADS, 8) void k_shuffle_tab(int64_t n, const uint32_t* __restrict__ cum, int kpad, int blk_words, int K,
                                                                   const uint32_t* __restrict__ keys, LibDom dom0, int nrows,
                                                                   uint8_t* __restrict__ slab_all, int pw, const int32_t* __restrict__ spot_of,
-                                                                  int tab_word0) {
+                                                                  int tab_word0, const uint32_t* __restrict__ tabs) {
     static_assert(!FIX || (SMALLK && NOMAP), "the FIX pair runs without a spot map and with K <= 126 only");
     extern __shared__ uint32_t s_lds[];
     uint32_t* s_cum = s_lds + blk_words;
@@ -324,7 +362,12 @@ __global__ __launch_bounds__(SHUF_TAB_THREADS, 8) void k_shuffle_tab(int64_t n, 
     const uint32_t* ksA = kgA + 8;
     const uint32_t* ksB = kgB + 8;
     const u16x2 BB = (u16x2)((unsigned short)dom.B);
-    {   // the two tables of this row pair: F_B <= Bmask < 2B, one conditional subtraction stores it mod B
+    if constexpr (PRETAB) {  // the two tables of this row pair as k_shuffle_tab_build left them: A * 4 rows of 16 bytes, linear
+        const int rows16 = (int)dom.A * 4;
+        const uint4* src = reinterpret_cast<const uint4*>(tabs) + (size_t)blockIdx.y * rows16;
+        uint4* dst = reinterpret_cast<uint4*>(s_lds + tab_word0);  // tab_word0 is a multiple of 8 words
+        for (int t = threadIdx.x; t < rows16; t += SHUF_TAB_THREADS) dst[t] = src[t];
+    } else {  // the two tables of this row pair: F_B <= Bmask < 2B, one conditional subtraction stores it mod B
         const u16x2 bsh = (u16x2)((unsigned short)dom.bsh);
         const int words = (int)dom.A * 8;
         for (int idx = threadIdx.x; idx < words; idx += SHUF_TAB_THREADS) {
@@ -414,11 +457,12 @@ __global__ __launch_bounds__(SHUF_TAB_THREADS, 8) void k_shuffle_tab(int64_t n, 
             uint32_t a4pk[2], bpk[2];  // sigma images of the word's two pairs, the high digits scaled by 4 (kept for the exact route)
 #pragma unroll
             for (int jj = 0; jj < 2; ++jj) {
-                const u16x2 t = gsb + __builtin_bit_cast(u16x2, f1[w * 2 + jj]);
+                const u16x2 t = add_nocarry(gsb, __builtin_bit_cast(u16x2, f1[w * 2 + jj]));  // gsb < B, T < B: < 2B <= 2^15
                 const u16x2 b = __builtin_elementwise_min(t, (u16x2)(t - BB));
                 const u16x2 k1 = __builtin_bit_cast(u16x2, ks[(w * 2 + jj) * 2 + 1]);
                 bpk[jj] = __builtin_bit_cast(uint32_t, b);
-                a4pk[jj] = __builtin_bit_cast(uint32_t, (u16x2)((gsa4 + shuf_tab_F2(b, k1, ash4, c1)) & am4));
+                // gsa4 < 4A, x >> ash4 < 4A: < 8A <= 2^13 (A <= SHUF_TAB_MAX_A)
+                a4pk[jj] = __builtin_bit_cast(uint32_t, (u16x2)(add_nocarry(gsa4, shuf_tab_F2(b, k1, ash4, c1)) & am4));
                 const uint32_t e0 = blk_at(a4pk[jj] & 0xFFFFu);
                 const uint32_t e1 = blk_at(a4pk[jj] >> 16);
                 if (jj == 0) {
@@ -877,6 +921,11 @@ int LabelShuffler::keygen(const char* timer, uint64_t seed, int64_t perm0, int n
     return SQGR_OK;
 }
 
+int LabelShuffler::ensure_tab_workspace(int B, int nb_max) {
+    if (B != 16 || has_libs || wide() || dom0.dom.A > SHUF_TAB_MAX_A) return SQGR_OK;  // launch_shuffle_raw never picks the table kernel
+    return tab_ws.ensure(tab_workspace_words((std::max(nb_max, 1) + 1) / 2));
+}
+
 int LabelShuffler::launch_shuffle_raw(int B, int nb, const uint32_t* keys, uint8_t* slab, hipStream_t st, bool independent, int pw) const {
     unsigned gx = (unsigned)ceil_div(n, 256);
     // ~96 blocks per CU over all batches of the launch, each walking several spots (grid stride): amortises the LDS table
@@ -943,6 +992,10 @@ int LabelShuffler::launch_shuffle_raw(int B, int nb, const uint32_t* keys, uint8
         // work) and keep k_shuffle.  Measured on MI355X, ms per launch, k_shuffle | k_shuffle_tab, 30 clusters — 1e6 spots: 16 rows
         // (7.6 trips) 0.137 | 0.158, 32 rows (15) 0.260 | 0.252, 64 rows 0.508 | 0.453, 160 rows 1.284 | 1.059; 105 600 spots
         // (A = 512): 64 rows (6.5 trips) 0.091 | 0.091, 160 rows (16) 0.202 | 0.193.
+        // With the FIX pair and the tables built once per launch the table kernel won at every size of a later sweep (30 clusters,
+        // eligible tables only) — 1e6 spots: 4 rows (3.8 trips) 0.047 | 0.045, 16 rows 0.139 | 0.108, 32 rows 0.259 | 0.184; 105 600
+        // spots: 16 rows (1.6 trips) 0.031 | 0.030, 64 rows 0.090 | 0.064 (profiles/shuffle_pretab_before_after.md).  The threshold
+        // stays until the instances that keep the sentinel test (K > 126, spot maps, skewed sizes) are swept too.
         const int cus = std::max(ctx->cu_count, 1);
         const int64_t block_trips = ceil_div(n, SHUF_TAB_THREADS) * (int64_t)gy;  // (block, trip) units of the launch
         const bool big = block_trips >= (int64_t)SHUF_TAB_MIN_TRIPS * 2 * cus;
@@ -965,12 +1018,29 @@ int LabelShuffler::launch_shuffle_raw(int B, int nb, const uint32_t* keys, uint8
             const unsigned cap = (unsigned)(tab_per_cu * cus) / gy + 1;
             const unsigned trips = (nblk + cap - 1) / cap;
             const unsigned tx = (nblk + trips - 1) / trips;
-#define SQGR_SHUFFLE_TAB(SK, NOMAP, FIX)                                                                                            \
-    do {                                                                                                                           \
-        SQGR_TRY(allow_lds(k_shuffle_tab<SK, NOMAP, FIX>, lds_tab));                                                               \
-        k_shuffle_tab<SK, NOMAP, FIX><<<dim3(tx, gy), SHUF_TAB_THREADS, lds_tab, st>>>(n, cum.p, kpad, blk_words, K, keys, dom0, nb, \
-                                                                                     slab, pw, spot_of.p, (int)tab_word0);       \
+            // the row pairs' tables built once per launch (k_shuffle_tab_build) instead of once per block.  SQGR_SHUFFLE_PRETAB (read
+            // at every call): 0 the in-block build, unset | 1 the prebuilt tables — every instance of the table kernel.  Same stream,
+            // inside this launch's timer bracket: the build's time is the shuffle's
+            const char* env_pre = getenv("SQGR_SHUFFLE_PRETAB");
+            const bool pretab = !(env_pre && atoi(env_pre) == 0);
+            if (pretab) {
+                const size_t need = tab_workspace_words((int)gy);
+                if (!tab_ws.p || tab_ws.n < need) {
+                    set_error("the table workspace holds %zu words, a launch of %u row pairs takes %zu (LabelShuffler::ensure_tab_workspace)",
+                              tab_ws.p ? tab_ws.n : (size_t)0, gy, need);
+                    return SQGR_ERR_INVALID;
+                }
+                k_shuffle_tab_build<<<dim3((unsigned)ceil_div((int64_t)A * 8, 256), gy), 256, 0, st>>>(keys, dom0.dom, nb, tab_ws.p);
+                SQGR_HIP(hipGetLastError());
+            }
+#define SQGR_SHUFFLE_TAB_P(SK, NOMAP, FIX, PRE)                                                                                          \
+    do {                                                                                                                                \
+        SQGR_TRY(allow_lds(k_shuffle_tab<SK, NOMAP, FIX, PRE>, lds_tab));                                                               \
+        k_shuffle_tab<SK, NOMAP, FIX, PRE><<<dim3(tx, gy), SHUF_TAB_THREADS, lds_tab, st>>>(n, cum.p, kpad, blk_words, K, keys, dom0, nb, \
+                                                                                          slab, pw, spot_of.p, (int)tab_word0, tab_ws.p); \
     } while (0)
+#define SQGR_SHUFFLE_TAB(SK, NOMAP, FIX) \
+    do { if (pretab) SQGR_SHUFFLE_TAB_P(SK, NOMAP, FIX, true); else SQGR_SHUFFLE_TAB_P(SK, NOMAP, FIX, false); } while (0)
             if (fix) {
                 SQGR_SHUFFLE_TAB(true, true, true);
             } else if (K <= 126) {
@@ -979,6 +1049,7 @@ int LabelShuffler::launch_shuffle_raw(int B, int nb, const uint32_t* keys, uint8
                 if (spot_of.p) SQGR_SHUFFLE_TAB(false, false, false); else SQGR_SHUFFLE_TAB(false, true, false);
             }
 #undef SQGR_SHUFFLE_TAB
+#undef SQGR_SHUFFLE_TAB_P
             SQGR_HIP(hipGetLastError());
             const uint32_t E = A * dom0.dom.B - (uint32_t)n;  // ranks of the domain outside [0, n)
             if (fix && E > 0) {  // same stream, inside this launch's timer bracket: its time is the shuffle's

@@ -84,6 +84,7 @@
 #define OP_LSHL(d) "v_lshlrev_b32 %" #d ", 3, %" #d "\n"
 #define OP_OR(d) "v_or_b32 %" #d ", %" #d ", %8\n"
 #define OP_ADDLSHL(d) "v_add_lshl_u32 %" #d ", %" #d ", %8, 3\n"
+#define OP_BITOP3(d) "v_bitop3_b32 %" #d ", %" #d ", %8, %9 bitop3:0x80\n"  // a & b & c
 #define OP_MAD64(d) "v_mad_u64_u32 v[20:21], vcc, %" #d ", %8, v[20:21]\n"
 
 VALU_KERNEL(k_fma, OP_FMA)
@@ -128,6 +129,7 @@ VALU_KERNEL(k_madu16, OP_MADU16)
 VALU_KERNEL(k_lshl, OP_LSHL)
 VALU_KERNEL(k_or, OP_OR)
 VALU_KERNEL(k_addlshl, OP_ADDLSHL)
+VALU_KERNEL(k_bitop3, OP_BITOP3)
 
 // ---- LDS rows: 16 ds_add_u32 (no return) per trip on 8 address registers; MODE selects the address pattern
 //   0: lane*4 (+ per-register offset)        conflict-free, the guide's ds_write_b32-class figure
@@ -257,6 +259,7 @@ int main(int argc, char** argv) {
     TV("v_lshlrev_b32", k_lshl);
     TV("v_or_b32", k_or);
     TV("v_add_lshl_u32", k_addlshl);
+    TV("v_bitop3_b32", k_bitop3);
     const double fma_rate = rows[0].winstr_per_s;
 
     std::vector<Row> lrows;
