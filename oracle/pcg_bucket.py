@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE — restatement in numpy of the *device's* bucketed replay of ``Generator.shuffle``
-(``csrc/sqgr_pcg_bucket.hip``), so that its re-ordering argument can be checked on the CPU against numpy itself.
+(``csrc/sqgr_pcg.hip``: k_pcg_draws_bucketed2 + k_pcg_apply_claims), so that its re-ordering argument can be checked on the CPU against numpy itself.
 
 numpy's shuffle (reference semantics: ``gr/_nhood.py:533-538`` -> ``Generator.shuffle``) is the reverse Fisher-Yates
 ``for i = n-1 .. 1: j = random_interval(i); swap(x[i], x[j])`` with masked rejection sampling over 32-bit halves of the PCG64

@@ -128,18 +128,14 @@ __device__ __forceinline__ uint32_t pair_index(uint32_t la, uint32_t lb, uint32_
 // term rides in the multiplier of the dot product: v_mad_u32_u16 forms {hi: bytes per cell, lo: (hi + 1) * bytes per cell / 2}
 // and v_dot2_u32_u16 multiplies it with {hi: lo, lo: hi} — five instructions per counter address instead of two.
 // The block's partial is then the LDS image itself (16-bit counters, no h + h^T pass): k_reduce16 expands it.
-// SQGR_COUNT_DOT2=0 (the three-instruction address path) and SQGR_COUNT_DEBUG=<mask> (probe variants of k_count): read once per
-// process, here, for every place that selects a count kernel
-static bool count_dot2() {
-    static const bool on = [] { const char* e = getenv("SQGR_COUNT_DOT2"); return !(e && atoi(e) == 0); }();
-    return on;
-}
+// B = 32 keeps the three-instruction address path of round 1.
+// SQGR_COUNT_DEBUG=<mask> (probe variants of k_count): read once per process, here, for every place that selects a count kernel
 static int count_debug() {
     static const int v = [] { const char* e = getenv("SQGR_COUNT_DEBUG"); return e ? atoi(e) : 0; }();
     return v;
 }
 
-template <int B, int MIN_WAVES, bool SELF, bool DOT2 = false, int DBG = 0, int CM = 0>  // DBG (developer probes, bit mask): 1 no atomics, 2 no row gathers, 4 no list loads
+template <int B, int MIN_WAVES, bool SELF, int DBG = 0, int CM = 0>  // DBG (developer probes, bit mask): 1 no atomics, 2 no row gathers, 4 no list loads
 __global__ __launch_bounds__(COUNT_THREADS, MIN_WAVES) void k_count(uint32_t nnz, const int2* __restrict__ coo,
                                                                     const uint8_t* __restrict__ slab_all, int64_t n, int K,
                                                                     int hist_words, uint32_t edges_per_block,
@@ -151,7 +147,8 @@ __global__ __launch_bounds__(COUNT_THREADS, MIN_WAVES) void k_count(uint32_t nnz
     __builtin_amdgcn_s_setprio(3);
     constexpr int BPL = B / 4;  // label bytes per lane
     constexpr int LOGW = CM ? 5 : ((B == 32) ? 7 : 6);  // log2(bytes of one pair's B counters)
-    static_assert(CM == 0 || (DOT2 && B == 16 && DBG == 0), "16-bit counters: the dot2 path at 16 permutations per pass");
+    constexpr bool DOT2 = (B == 16);
+    static_assert(CM == 0 || (DOT2 && DBG == 0), "16-bit counters: the dot2 path at 16 permutations per pass");
     const int tid = threadIdx.x;
     for (int i = tid; i < hist_words; i += COUNT_THREADS) hist[i] = 0;
     __syncthreads();
@@ -191,7 +188,6 @@ __global__ __launch_bounds__(COUNT_THREADS, MIN_WAVES) void k_count(uint32_t nnz
     const uint32_t half_sh0 = CM ? 16u * (el & 1u) : 0u, half_sh1 = CM ? 16u * ((el + 1u) & 1u) : 0u;
     const uint32_t qoff = q * BPL;
     char* hist_bytes = reinterpret_cast<char*>(hist);
-    static_assert(!DOT2 || B == 16, "the dot2 address path is written for 16 permutations per pass");
     uint32_t sel[BPL];  // DOT2: byte (s + el) & 3 of the b row -> bits 0..7, of the a row -> bits 16..23, zeros elsewhere
 #pragma unroll
     for (int s = 0; s < BPL; ++s) sel[s] = 0x0c000c00u | ((4u + ((s + el) & 3u)) << 16) | ((s + el) & 3u);
@@ -420,7 +416,7 @@ __global__ __launch_bounds__(COUNT_THREADS, MIN_WAVES) void k_count(uint32_t nnz
     }
 }
 
-// k_count<16, MIN_WAVES, false, true> with another front end: the SEGMENT list of a lattice graph (sqgr_graph::ensure_seg) instead of
+// k_count<16, MIN_WAVES, false> with another front end: the SEGMENT list of a lattice graph (sqgr_graph::ensure_seg) instead of
 // the half list.  An entry (r0, d, mask) stands for the up to 16 half edges (r0 + j, r0 + j + d), so the sixteen `a` rows are 256
 // contiguous slab bytes and the sixteen `b` rows are 256 contiguous bytes 16 d further: lane l of a wave (edge j = l >> 2, word l & 3
 // of the row, as in k_count) loads slab + 16 r0 + 4 l and that + 16 d — two fully coalesced dword loads per entry, 4 L1 accesses
@@ -1298,7 +1294,7 @@ struct sqgr_nhood {
         return want;
     }
     // The segment path (k_count_seg over sqgr_graph::seg, then k_count over the residual edges): taken iff the plan would otherwise
-    // run k_count<16, ., false, true> with 32-bit counters on a half list without self loops and the segments cover at least 90 % of
+    // run k_count<16, ., false> with 32-bit counters on a half list without self loops and the segments cover at least 90 % of
     // the half edges.  SQGR_COUNT_SEGMENTS (read at every call by resolve_tuning): 0 never, 2 required — whatever the coverage, and
     // a plan that is not eligible is an error that names the reason —, unset | 1: automatic.
     bool seg_active = false;
@@ -1359,7 +1355,7 @@ int sqgr_nhood::resolve_tuning() {
         const char* why = nullptr;
         if (wide() || B != 16) why = "32-wide label rows or more than 256 clusters";
         else if (be() != 16 || cm()) why = "the counters of 16 permutations do not fit LDS in 32 bits (more than 50 clusters)";
-        else if (!count_dot2() || count_debug() != 0) why = "SQGR_COUNT_DOT2=0 or a probe variant is selected";
+        else if (count_debug() != 0) why = "a probe variant is selected (SQGR_COUNT_DEBUG)";
         else {
             // automatic: the coverage is counted on the CSR first (one pass, no sort, 8 bytes of workspace), so that a graph without
             // segments — kNN, Delaunay, a Z-order twin — never pays for the list; required: the list whatever it covers
@@ -1486,11 +1482,11 @@ int sqgr_nhood::count_batches(int nb, int buf) {
         if (nres_blk) {  // the half edges outside the segments: k_count as on the half list, partial slots behind the segment blocks'
             const uint32_t epb_r = (uint32_t)(ceil_div(ceil_div((int64_t)nres, nres_blk), 1024) * 1024);
             if (lds * 2 <= LDS_BUDGET) {
-                SQGR_TRY(allow_lds((k_count<16, 8, false, true>), lds));
-                k_count<16, 8, false, true><<<dim3(nres_blk, nb), COUNT_THREADS, lds, st>>>(nres, g->seg_res.p, slab_p, n, K, hw, epb_r, nres, 1, partial.p, nseg_blk);
+                SQGR_TRY(allow_lds((k_count<16, 8, false>), lds));
+                k_count<16, 8, false><<<dim3(nres_blk, nb), COUNT_THREADS, lds, st>>>(nres, g->seg_res.p, slab_p, n, K, hw, epb_r, nres, 1, partial.p, nseg_blk);
             } else {
-                SQGR_TRY(allow_lds((k_count<16, 4, false, true>), lds));
-                k_count<16, 4, false, true><<<dim3(nres_blk, nb), COUNT_THREADS, lds, st>>>(nres, g->seg_res.p, slab_p, n, K, hw, epb_r, nres, 1, partial.p, nseg_blk);
+                SQGR_TRY(allow_lds((k_count<16, 4, false>), lds));
+                k_count<16, 4, false><<<dim3(nres_blk, nb), COUNT_THREADS, lds, st>>>(nres, g->seg_res.p, slab_p, n, K, hw, epb_r, nres, 1, partial.p, nseg_blk);
             }
         }
         SQGR_HIP(hipGetLastError());
@@ -1598,8 +1594,8 @@ int sqgr_nhood::count_batches(int nb, int buf) {
             LaunchTimer t(ctx, half ? "nhood_count_c16_half" : "nhood_count_c16");
 #define SQGR_COUNT16(MW, SELF, CM)                                                                                             \
     do {                                                                                                                       \
-        SQGR_TRY(allow_lds((k_count<16, MW, SELF, true, 0, CM>), lds));                                                        \
-        k_count<16, MW, SELF, true, 0, CM><<<grid, COUNT_THREADS, lds, st>>>(m, list, slab_p, n, K, pw16, epb, self_begin, 0, partial.p); \
+        SQGR_TRY(allow_lds((k_count<16, MW, SELF, 0, CM>), lds));                                                        \
+        k_count<16, MW, SELF, 0, CM><<<grid, COUNT_THREADS, lds, st>>>(m, list, slab_p, n, K, pw16, epb, self_begin, 0, partial.p); \
     } while (0)
 #define SQGR_COUNT16_S(MW, CM) \
     do { if (self) SQGR_COUNT16(MW, true, CM); else SQGR_COUNT16(MW, false, CM); } while (0)
@@ -1615,9 +1611,6 @@ int sqgr_nhood::count_batches(int nb, int buf) {
         }
 #define SQGR_COUNT(BB, MW, SELF) \
     k_count<BB, MW, SELF><<<grid, COUNT_THREADS, lds, st>>>(m, list, slab_p, n, K, hw, epb, self_begin, addt, partial.p)
-#define SQGR_COUNT_D(BB, MW, SELF) \
-    k_count<BB, MW, SELF, true><<<grid, COUNT_THREADS, lds, st>>>(m, list, slab_p, n, K, hw, epb, self_begin, addt, partial.p)
-        const bool dot2 = count_dot2();
         if (B == 32) {
             LaunchTimer t(ctx, half ? "nhood_count_b32_half" : "nhood_count_b32");
             if (self) {
@@ -1630,24 +1623,14 @@ int sqgr_nhood::count_batches(int nb, int buf) {
         } else {
             LaunchTimer t(ctx, half ? "nhood_count_b16_half" : (split_list ? "nhood_count_b16_split" : "nhood_count_b16"));
             const int dbg = count_debug();
-            if (dot2 && dbg && lds * 2 <= LDS_BUDGET && !self) {
+            if (dbg && lds * 2 <= LDS_BUDGET && !self) {
 #define SQGR_COUNT_DBG(D) \
-    case D: k_count<16, 8, false, true, D><<<grid, COUNT_THREADS, lds, st>>>(m, list, slab_p, n, K, hw, epb, self_begin, addt, partial.p); break
+    case D: k_count<16, 8, false, D><<<grid, COUNT_THREADS, lds, st>>>(m, list, slab_p, n, K, hw, epb, self_begin, addt, partial.p); break
                 switch (dbg) {
                     SQGR_COUNT_DBG(1); SQGR_COUNT_DBG(2); SQGR_COUNT_DBG(3); SQGR_COUNT_DBG(4); SQGR_COUNT_DBG(5); SQGR_COUNT_DBG(6);
-                    default: k_count<16, 8, false, true, 7><<<grid, COUNT_THREADS, lds, st>>>(m, list, slab_p, n, K, hw, epb, self_begin, addt, partial.p);
+                    default: k_count<16, 8, false, 7><<<grid, COUNT_THREADS, lds, st>>>(m, list, slab_p, n, K, hw, epb, self_begin, addt, partial.p);
                 }
 #undef SQGR_COUNT_DBG
-            } else if (dot2) {
-                if (lds * 2 <= LDS_BUDGET) {
-                    if (self) SQGR_COUNT_D(16, 8, true); else SQGR_COUNT_D(16, 8, false);
-                } else if (self) {
-                    SQGR_TRY(allow_lds(k_count<16, 4, true, true>, lds));
-                    SQGR_COUNT_D(16, 4, true);
-                } else {
-                    SQGR_TRY(allow_lds(k_count<16, 4, false, true>, lds));
-                    SQGR_COUNT_D(16, 4, false);
-                }
             } else if (lds * 2 <= LDS_BUDGET) {
                 if (self) SQGR_COUNT(16, 8, true); else SQGR_COUNT(16, 8, false);
             } else if (self) {
@@ -1659,7 +1642,6 @@ int sqgr_nhood::count_batches(int nb, int buf) {
             }
         }
 #undef SQGR_COUNT
-#undef SQGR_COUNT_D
     } else {  // K*K counters do not fit LDS: device-scope atomics into ONE histogram per batch
         const int gblk = std::max(nblk, 64);
         const int64_t epb = ceil_div(nnz, gblk);
@@ -2022,7 +2004,7 @@ static int run_pcg64_impl(sqgr_nhood* plan, const uint64_t* pcg_states, int64_t 
         const int64_t stride = chunk;  // multiple of 64 => 16-byte aligned slab gathers
         // without libraries the shuffled ROWS go straight into the slab (k_rows_to_slab); with libraries (position != spot) through
         // the column matrix as before
-        const bool via_rows = !sh.has_libs && pcg_rows_available();
+        const bool via_rows = !sh.has_libs;
         if (!via_rows) SQGR_TRY(p->wcol.ensure((size_t)n * stride));
         SQGR_TRY(p->pcg_states.ensure((size_t)chunk * 4));
         const int64_t per_launch = (int64_t)p->nbatch * B;

@@ -11,7 +11,6 @@ struct PcgWorkspace {
     DevBuf<uint64_t> jump;  // [34][4] LCG jump-ahead table of the wave-per-permutation kernel
     DevBuf<uint8_t> rows;   // [permutation][n_pad] row-major shuffle workspace
     DevBuf<uint32_t> span;  // {0, n}: the single "library" of a plain permutation
-    DevBuf<int32_t> cols;   // column workspace of the one-thread-per-permutation kernel (SQGR_PCG_KERNEL=lane)
     // the bucketed replay (long arrays): time-ordered swap records per (permutation, phase, 64-record block), their directory
     // (range | count << 8 | ordinal << 16 per block) and the blocks written per phase; library geometry cached from the device
     DevBuf<uint32_t> recs, dir, nblk, lib_phase;
@@ -25,8 +24,7 @@ struct PcgWorkspace {
 int pcg_shuffle_labels(sqgr_ctx* ctx, PcgWorkspace& ws, int64_t n, int n_libs, const uint32_t* lib_off_dev, const uint8_t* base_pos_dev,
                        const uint64_t* states_dev, int64_t pc, int64_t stride, uint8_t* W, hipStream_t st, const char* timer_name);
 
-// The same arrays as ROWS: ws.rows[q * (*row_stride) + pos] (no transposition; not for SQGR_PCG_KERNEL=lane: pcg_rows_available()).
-bool pcg_rows_available();
+// The same arrays as ROWS: ws.rows[q * (*row_stride) + pos] (no transposition).
 int pcg_shuffle_rows(sqgr_ctx* ctx, PcgWorkspace& ws, int64_t n, int n_libs, const uint32_t* lib_off_dev, const uint8_t* base_pos_dev,
                      const uint64_t* states_dev, int64_t pc, hipStream_t st, const char* timer_name, int64_t* row_stride);
 

@@ -20,166 +20,10 @@ namespace sqgr {
 // algorithm — PCG64 (128-bit LCG, XSL-RR output, 32-bit halves buffered low first) driving the reverse
 // Fisher-Yates of Generator.shuffle with masked rejection sampling — from the generator state that
 // `np.random.default_rng(SeedSequence(seed).spawn(n)[p])` starts in (computed by numpy on the host, 32 bytes per
-// permutation).  Two kernels: k_pcg_shuffle_wave (default, one WAVE per permutation, further down) and the simpler
-// k_pcg_shuffle (SQGR_PCG_KERNEL=lane: ONE THREAD PER PERMUTATION, each on its own column of a [position][permutation]
-// matrix; the access to row i is coalesced across threads, the access to row j is the scattered one) — kept as an
-// independent implementation the tests compare against.
-struct Pcg64 {
-    uint64_t lo, hi, inc_lo, inc_hi;
-    uint32_t buf;
-    bool has;
-};
-
-__device__ __forceinline__ uint64_t pcg64_next64(Pcg64& g) {
-    const uint64_t ML = 0x4385DF649FCCF645ull, MH = 0x2360ED051FC65DA4ull;  // PCG_DEFAULT_MULTIPLIER_128
-    const uint64_t plo = g.lo * ML;
-    const uint64_t phi = __umul64hi(g.lo, ML) + g.lo * MH + g.hi * ML;
-    const uint64_t nlo = plo + g.inc_lo;
-    const uint64_t nhi = phi + g.inc_hi + (nlo < plo ? 1ull : 0ull);
-    g.lo = nlo;
-    g.hi = nhi;
-    const uint64_t x = nhi ^ nlo;
-    const unsigned rot = (unsigned)(nhi >> 58);
-    return (x >> rot) | (x << ((64u - rot) & 63u));
-}
-
-__device__ __forceinline__ uint32_t pcg64_next32(Pcg64& g) {
-    if (g.has) {
-        g.has = false;
-        return g.buf;
-    }
-    const uint64_t v = pcg64_next64(g);
-    g.has = true;
-    g.buf = (uint32_t)(v >> 32);
-    return (uint32_t)v;
-}
-
-constexpr int PCG_UNROLL = 8;   // swaps replayed in registers per trip (2*PCG_UNROLL loads in flight)
-constexpr int PCG_BLOCK = 32;   // steps whose draws are generated together (multiple of PCG_UNROLL)
-
-// W[pos * stride + p]: column p = the array numpy would shuffle for permutation p (positions grouped by library,
-// libraries in category order == the order `_shuffle_group` visits them, gr/_utils.py:207-212).
+// permutation).  Two paths: k_pcg_shuffle_wave (one WAVE per permutation, swaps applied in numpy's own order; arrays below
+// 65 536 positions, Generator.permutation, and the fallback when the records of the other path find no memory) and the
+// bucketed replay k_pcg_draws_bucketed2 + k_pcg_apply_claims (long arrays, further down).
 //
-// Two things keep the lanes of a wave busy although every lane runs its own sequential Fisher-Yates:
-//  * rejection sampling is decoupled from the steps: the draws j of PCG_BLOCK consecutive steps are produced in one
-//    per-lane loop (a lane that needs fewer draws idles only until the slowest lane of the wave has its PCG_BLOCK
-//    draws, instead of after every single step) and parked in LDS;
-//  * the draws depend on the generator only, so the 2*PCG_UNROLL loads of a trip are issued before any swap is
-//    applied and the swaps are replayed in registers.  Step t exchanges positions i-t and j_t; i-t is above
-//    everything later steps touch, so its value is final after step t; a j position may recur (j_e == j_t, or
-//    j_e == i-t for e < t) and then takes the value the earlier step left there instead of the stale load.
-template <typename T, bool ARANGE>
-__global__ __launch_bounds__(64) void k_pcg_shuffle(int64_t n, int n_libs, const uint32_t* __restrict__ lib_off,
-                                                    const T* __restrict__ base_pos, const uint64_t* __restrict__ states,
-                                                    int64_t P, int64_t stride, T* __restrict__ W) {
-    __shared__ uint32_t s_j[PCG_BLOCK][64];
-    const int lane = threadIdx.x;
-    const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (p >= P) return;
-    Pcg64 g;
-    g.hi = states[4 * p + 0];
-    g.lo = states[4 * p + 1];
-    g.inc_hi = states[4 * p + 2];
-    g.inc_lo = states[4 * p + 3];
-    g.has = false;
-    g.buf = 0;
-    T* col = W + p;
-    for (int64_t e = 0; e < n; ++e) col[e * stride] = ARANGE ? (T)e : base_pos[e];
-    for (int l = 0; l < n_libs; ++l) {
-        const uint32_t off = lib_off[l];
-        const uint32_t m = lib_off[l + 1] - off;
-        if (m < 2) continue;
-        T* sub = col + (int64_t)off * stride;
-        uint32_t mask = m - 1;  // smallest all-ones mask >= i, maintained as i decreases
-        mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
-        uint32_t i = m - 1;
-        while (i >= (uint32_t)PCG_BLOCK) {
-            // ---- draws of steps i, i-1, ..., i-PCG_BLOCK+1 (numpy: `while ((v = next_uint32() & mask) > max);`)
-            {
-                int t = 0;
-                uint32_t it = i;
-                if ((mask >> 1) >= it) mask >>= 1;
-                if (g.has) {  // high half left over from the previous block
-                    g.has = false;
-                    const uint32_t c = g.buf & mask;
-                    if (c <= it) {
-                        s_j[t][lane] = c;
-                        ++t;
-                        --it;
-                        if ((mask >> 1) >= it) mask >>= 1;
-                    }
-                }
-                while (t < PCG_BLOCK) {
-                    const uint64_t v = pcg64_next64(g);
-                    const uint32_t c0 = (uint32_t)v & mask;
-                    if (c0 <= it) {
-                        s_j[t][lane] = c0;
-                        ++t;
-                        --it;
-                        if ((mask >> 1) >= it) mask >>= 1;
-                    }
-                    if (t < PCG_BLOCK) {
-                        const uint32_t c1 = (uint32_t)(v >> 32) & mask;
-                        if (c1 <= it) {
-                            s_j[t][lane] = c1;
-                            ++t;
-                            --it;
-                            if ((mask >> 1) >= it) mask >>= 1;
-                        }
-                    } else {  // the block is complete after the low half: numpy keeps the high half buffered
-                        g.has = true;
-                        g.buf = (uint32_t)(v >> 32);
-                    }
-                }
-            }
-            // ---- apply: PCG_UNROLL swaps per trip
-            constexpr int U = PCG_UNROLL;
-#pragma unroll 1
-            for (int t0 = 0; t0 < PCG_BLOCK; t0 += U) {
-                const uint32_t ib = i - t0;
-                uint32_t j[U];
-                T vi[U], vj[U];
-#pragma unroll
-                for (int t = 0; t < U; ++t) j[t] = s_j[t0 + t][lane];
-#pragma unroll
-                for (int t = 0; t < U; ++t) {
-                    vi[t] = sub[(int64_t)(ib - t) * stride];
-                    vj[t] = sub[(int64_t)j[t] * stride];
-                }
-                T at_i[U], at_j[U];  // values left at position ib-t resp. j_t by step t
-#pragma unroll
-                for (int t = 0; t < U; ++t) {
-                    T cur_i = vi[t], cur_j = vj[t];
-#pragma unroll
-                    for (int e = 0; e < t; ++e) {  // a later e overrides an earlier one
-                        cur_i = (j[e] == ib - t) ? at_j[e] : cur_i;
-                        cur_j = (j[e] == j[t]) ? at_j[e] : cur_j;
-                    }
-                    at_i[t] = cur_j;
-                    at_j[t] = cur_i;
-                }
-                // j stores in step order (a recurring position keeps the last one), then the final i stores on top
-#pragma unroll
-                for (int t = 0; t < U; ++t) sub[(int64_t)j[t] * stride] = at_j[t];
-#pragma unroll
-                for (int t = 0; t < U; ++t) sub[(int64_t)(ib - t) * stride] = at_i[t];
-            }
-            i -= PCG_BLOCK;
-            // the mask was advanced to step i-PCG_BLOCK's bound already (idempotent update at the top of the next block)
-        }
-        for (; i >= 1; --i) {
-            if ((mask >> 1) >= i) mask >>= 1;
-            uint32_t j;
-            do {
-                j = pcg64_next32(g) & mask;
-            } while (j > i);
-            const T a = sub[(int64_t)i * stride], b = sub[(int64_t)j * stride];
-            sub[(int64_t)i * stride] = b;
-            sub[(int64_t)j * stride] = a;
-        }
-    }
-}
-
 // ---- one WAVE per permutation ------------------------------------------------------------------------------------
 // The sequential chain of Fisher-Yates is only apparent:
 //  (1) the raw generator outputs are a pure function of the stream position (LCG jump-ahead: state_k = A_k*state +
@@ -193,8 +37,8 @@ __global__ __launch_bounds__(64) void k_pcg_shuffle(int64_t n, int n_libs, const
 //      exchanges.
 // Both paths consume the identical draw sequence as numpy (32-bit halves, low first; a library that ends mid-chunk leaves
 // the remaining draws to the next one; a mask change or the last 192 steps take the draws one by one).
-// Layout: R[p][row_stride] (a permutation's array is contiguous).  ~45 steps per trip; measured 12x the
-// one-thread-per-permutation kernel at Squidpy's default n_perms = 1000 (1e5 spots: 4.0 ms vs 48 ms).
+// Layout: R[p][row_stride] (a permutation's array is contiguous).  ~45 steps per trip; measured 12x a
+// one-thread-per-permutation kernel (retired: DESIGN.md §4) at Squidpy's default n_perms = 1000 (1e5 spots: 4.0 ms vs 48 ms).
 struct U128 {
     uint64_t hi, lo;
 };
@@ -466,18 +310,14 @@ __global__ __launch_bounds__(64) void k_pcg_shuffle_wave(int64_t n, int64_t row_
 //  * position i is read only by step i itself and by earlier steps e > i with j_e == i — those lie in range r == f; no later
 //    step touches i again (j_e <= e < i).  So a phase may apply its swaps RANGE BY RANGE: first the window range r == f (both
 //    sides inside the phase's own S positions), then every range r < f in any order, time order inside a range.
-// k_pcg_draws_bucketed (G, one wave per permutation) generates the draws with the exact acceptance logic of the wave kernel and
+// k_pcg_draws_bucketed2 (G, one wave per permutation) generates the draws with the acceptance logic of the wave kernel and
 // appends (j mod S | (i mod S) << 16) to time-ordered lists per (phase, range), in 64-record blocks: records
 // [perm][phase][block][64], directory entry per block = range | count << 8 | ordinal-within-range << 16.
-// k_pcg_apply_bucketed (A, one 1024-lane workgroup per permutation) walks the phases from the top: window and one range at a
-// time in LDS (coalesced 64 KB loads and stores), the records of a (phase, range) list applied 1024 at a time in ROUNDS: a
-// record goes when it is the earliest pending record of the chunk on its j slot (hashed tags, atomic max of epoch | 1023 - lane)
-// and — in the window range — no earlier pending record writes to its i slot; the others wait for the next round (~3.5 rounds
-// per chunk at 1e6 positions).  Traffic per permutation: ranges 16 phases x ~0.5 MB x 2 + records 2 x 4.3 MB.
+// k_pcg_apply_claims (A, one 1024-lane workgroup per permutation) walks the phases from the top: window and one range at a
+// time in LDS (coalesced 64 KB loads and stores), the records of a (phase, range) list applied a chunk of 2048 at a time: a
+// record whose positions no other record of the chunk touches swaps at once, the others are queued and go in time order (see
+// the kernel).  Traffic per permutation: ranges 16 phases x ~0.5 MB x 2 + records 2 x 4.3 MB.
 constexpr int PCGB_MAX_RANGES = 64;   // ranges per library (lane r of the generator wave keeps range r's cursors)
-constexpr int PCGB_RING = 128;        // staging ring per range (records)
-constexpr int PCGB_SLOTS = 3328;      // conflict tags of the apply kernel at 65536-position windows (two buffers: rounds alternate); shorter
-                                      // windows leave more of the 160 KB of LDS to the tags: PcgBucketGeom::slots
 constexpr int PCGB_CHUNK_BLOCKS = 32; // 64-record blocks per chunk of the apply kernel: two records per lane
 constexpr int PCGB_THREADS = 1024;
 
@@ -486,192 +326,25 @@ struct PcgBucketGeom {
     int n_ranges;          // max over libraries of ceil(m / S)
     int bcap;              // blocks per phase: S / 64 + n_ranges (rounded up when S < 64)
     int phases;            // phases of all libraries of one permutation
-    int slots;             // conflict tags per buffer of the apply kernel (two buffers)
     int qcap;              // k_pcg_apply_claims: queue entries in use (<= PCGQ_CAP; SQGR_PCG_QUEUE_CAP: tests of the spill path)
 };
 
 __device__ __forceinline__ uint32_t lane_get(uint32_t v, uint32_t src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)src); }
 
-__global__ __launch_bounds__(64) void k_pcg_draws_bucketed(int n_libs, const uint32_t* __restrict__ lib_off, const uint32_t* __restrict__ lib_phase,
-                                                           const uint64_t* __restrict__ states, const uint64_t* __restrict__ jump, int64_t P,
-                                                           PcgBucketGeom geo, uint32_t* __restrict__ recs, uint32_t* __restrict__ dir,
-                                                           uint32_t* __restrict__ nblk, int force_slow) {
-    extern __shared__ uint32_t s_stage[];  // [n_ranges][PCGB_RING]
-    __shared__ uint64_t sA[PCGW_TAB][2], sD[PCGW_TAB][2];
-    __shared__ uint32_t sJ[64];
-    __shared__ unsigned long long s_lanes[PCGB_MAX_RANGES];  // per range: the lanes whose record goes there (zero between appends)
-    const int lane = threadIdx.x;
-    s_lanes[lane] = 0ull;
-    const uint32_t logS = (uint32_t)geo.logS, SM = (1u << logS) - 1u;
-    const int64_t p = blockIdx.x;
-    if (p >= P) return;
-    U128 s, inc;
-    s.hi = states[4 * p + 0];
-    s.lo = states[4 * p + 1];
-    inc.hi = states[4 * p + 2];
-    inc.lo = states[4 * p + 3];
-    if (lane < PCGW_TAB) {
-        U128 a, g;
-        a.hi = jump[4 * lane + 0];
-        a.lo = jump[4 * lane + 1];
-        g.hi = jump[4 * lane + 2];
-        g.lo = jump[4 * lane + 3];
-        const U128 d = mul128_lo(g, inc);
-        sA[lane][0] = a.hi;
-        sA[lane][1] = a.lo;
-        sD[lane][0] = d.hi;
-        sD[lane][1] = d.lo;
-    }
-    uint32_t* const rec_p = recs + (size_t)p * geo.phases * geo.bcap * 64;
-    uint32_t* const dir_p = dir + (size_t)p * geo.phases * geo.bcap;
-    uint32_t* const nblk_p = nblk + (size_t)p * geo.phases;
-    // lane r keeps the cursors of range r: records staged, ring head, blocks flushed in this phase
-    uint32_t c_cnt = 0, c_head = 0, c_ord = 0;
-    uint32_t nb = 0;   // blocks written in the current phase (uniform)
-    uint32_t ph = 0;   // global index of the current phase (uniform)
-    auto flush_block = [&](uint32_t r0, uint32_t head, uint32_t count) {  // uniform arguments
-        const uint32_t v = s_stage[r0 * PCGB_RING + ((head + (uint32_t)lane) & (PCGB_RING - 1))];
-        uint32_t* dst = rec_p + ((size_t)ph * geo.bcap + nb) * 64;
-        const uint32_t ordinal = lane_get(c_ord, r0);
-        if ((uint32_t)lane < count) dst[lane] = v;
-        if (lane == 0) dir_p[(size_t)ph * geo.bcap + nb] = r0 | (count << 8) | (ordinal << 16);
-        if ((uint32_t)lane == r0) ++c_ord;
-        ++nb;
-    };
-    auto end_phase = [&](uint32_t f) {  // the partial blocks of ranges 0..f, then the phase's block count
-        for (uint32_t r0 = 0; r0 <= f; ++r0) {
-            const uint32_t cnt = lane_get(c_cnt, r0);
-            if (cnt > 0u) flush_block(r0, lane_get(c_head, r0), cnt);
-        }
-        if (lane == 0) nblk_p[ph] = nb;
-        c_cnt = 0;
-        c_head = 0;
-        c_ord = 0;
-        nb = 0;
-    };
-    // append the records of the lanes with `in` set (lane order == time order) to their ranges' rings; full blocks go out.
-    // The lanes of a range find each other through a 64-bit lane mask per range in LDS (one ds_or per record, one read): the
-    // rank of a record among its range's records of this trip is a count of the mask bits below its lane, the owner lane of a
-    // range adds the population count to its cursor — no loop over the ranges (a first version walked them one by one and made
-    // this kernel issue-bound at ~2000 clk per trip).
-    auto append = [&](bool in, uint32_t iloc, uint32_t jj) {
-        const uint32_t r = jj >> logS;
-        const uint32_t rec = (jj & SM) | (iloc << 16);
-        if (in) atomicOr(&s_lanes[r], 1ull << lane);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        const unsigned long long mk = in ? s_lanes[r] : 0ull;
-        const unsigned long long own = (lane < geo.n_ranges) ? s_lanes[lane] : 0ull;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (lane < geo.n_ranges) s_lanes[lane] = 0ull;  // re-armed for the next call
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-        const uint32_t cur = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(r << 2), (int)(c_cnt | (c_head << 8)));  // the cursors of MY range
-        if (in) s_stage[r * PCGB_RING + (((cur >> 8) + (cur & 0xffu) + rank) & (PCGB_RING - 1))] = rec;
-        c_cnt += (uint32_t)__popcll(own);
-        uint64_t full = __ballot(c_cnt >= 64u);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the rings are read back by other lanes of this wave
-        for (; full != 0ull; full &= full - 1ull) {
-            const uint32_t r0 = (uint32_t)__builtin_ctzll(full);
-            flush_block(r0, lane_get(c_head, r0), 64u);
-            if ((uint32_t)lane == r0) {
-                c_cnt -= 64u;
-                c_head = (c_head + 64u) & (PCGB_RING - 1);
-            }
-        }
-    };
-    uint32_t half = 0;
-    U128 sk;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    uint32_t raw = pcgw_draw(s, half, lane, sA, sD, sk);
-    for (int l = 0; l < n_libs; ++l) {
-        const uint32_t off = lib_off[l];
-        const uint32_t m = lib_off[l + 1] - off;
-        if (m < 2) continue;
-        uint32_t mask = m - 1;
-        mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
-        uint32_t i = m - 1;
-        uint32_t f_cur = i >> logS;
-        ph = lib_phase[l] + f_cur;
-        while (i >= 1) {
-            uint32_t used = 64, nacc = 0, it = i;
-            bool valid = false;
-            uint32_t ipos = 0, jj = 0;
-            const bool general = force_slow || i < 192u || (mask >> 1) >= i - 64u;
-            if (!general) {  // (see k_pcg_shuffle_wave: sure / ambiguous candidates, decided from the running count)
-                const uint32_t c = raw & mask;
-                const bool sure = c <= i - 64u;
-                const uint64_t ambm = __ballot(!sure && c <= i);
-                uint64_t accm = __ballot(sure);
-                for (uint64_t rem = ambm; rem != 0ull; rem &= rem - 1ull) {
-                    const int dd = __builtin_ctzll(rem);
-                    const uint32_t cd = lane_get(c, (uint32_t)dd);
-                    const uint32_t before = (uint32_t)__popcll(accm & ((1ull << dd) - 1ull));
-                    if (cd <= i - before) accm |= 1ull << dd;
-                }
-                valid = (accm >> lane) & 1ull;
-                const uint32_t t = __builtin_amdgcn_mbcnt_hi((uint32_t)(accm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)accm, 0u));
-                nacc = (uint32_t)__popcll(accm);
-                it = i - nacc;
-                ipos = i - t;
-                jj = c;
-            } else {
-                uint32_t t = 0;
-                for (int dd = 0; dd < 64; ++dd) {
-                    const uint32_t c = lane_get(raw, (uint32_t)dd) & mask;
-                    if (c <= it) {
-                        if (lane == 0) sJ[t] = c;
-                        ++t;
-                        --it;
-                        if ((mask >> 1) >= it) mask >>= 1;
-                        if (it == 0u) {
-                            used = (uint32_t)dd + 1u;
-                            break;
-                        }
-                    }
-                }
-                nacc = t;
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                valid = (uint32_t)lane < nacc;
-                ipos = i - (uint32_t)lane;
-                jj = valid ? sJ[lane] : 0u;
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            }
-            if (nacc > 0u) {
-                const uint32_t f_last = (it + 1u) >> logS;  // phase of the trip's last step
-                for (uint32_t f = f_cur;; --f) {
-                    append(valid && (ipos >> logS) == f, ipos & SM, jj);
-                    if (f == f_last) break;
-                    end_phase(f);
-                    --ph;
-                }
-                f_cur = f_last;
-            }
-            i = it;
-            if (i >= 1u && (i >> logS) != f_cur) {  // the next step opens a new phase
-                end_phase(f_cur);
-                --ph;
-                f_cur = i >> logS;
-            }
-            pcgw_advance(s, half, sk, used);
-            raw = pcgw_draw(s, half, lane, sA, sD, sk);
-        }
-        end_phase(f_cur);  // f_cur == 0 here: the library's last phase
-    }
-}
-
 // ---- the draw generator, 128 raw draws per trip (round 6) ---------------------------------------------------------------
-// k_pcg_draws_bucketed spends most of a trip on bookkeeping that does not depend on the number of draws (uniform branches,
-// cursor updates, the stream position: ~250 instructions of which 12 are the 128-bit multiply) and computes every LCG state in
-// two lanes, one per 32-bit half.  Here lane l advances to state l + 1 once and takes BOTH halves — slot 2l (low half) and
-// slot 2l + 1 (high half), numpy's order — so a trip consumes 128 draws (127 when the low half of the first state was used
-// before: after a full trip the stream always stands at a state boundary).  The acceptance, the running count, the phase
-// crossings and the time order of the records appended to a range's list are the ones of the 64-draw kernel, on pairs of lane
-// masks: slot (l, h) comes before (l', h') when l < l' or l == l' and h < h'.
+// Most of a trip is bookkeeping that does not depend on the number of draws (uniform branches, cursor updates, the stream
+// position: ~250 instructions of which 12 are the 128-bit multiply), and the wave kernel's one draw per lane computes every LCG
+// state in two lanes, one per 32-bit half.  Here lane l advances to state l + 1 once and takes BOTH halves — slot 2l (low half)
+// and slot 2l + 1 (high half), numpy's order — so a trip consumes 128 draws (127 when the low half of the first state was used
+// before: after a full trip the stream always stands at a state boundary).  The acceptance and the running count are the wave
+// kernel's, on pairs of lane masks: slot (l, h) comes before (l', h') when l < l' or l == l' and h < h'.  (A generator of 64
+// draws per trip, rounds 4-5, was retired: DESIGN.md §4.)
 constexpr int PCGW_TAB2 = 65;     // jump distances 0..64
-// One wavefront per permutation is bound by the latencies of its own instruction stream, so the kernel lives on occupancy (measured:
-// 8 KB more LDS per wavefront cost the 64-draw kernel 49.7 -> 73.4 ms per 8192 permutations).  LDS per wavefront here: a 64-record
+// One wavefront per permutation is bound by the latencies of its own instruction stream, so the kernel lives on occupancy (measured
+// on the 64-draw generator: 8 KB more LDS per wavefront, 49.7 -> 73.4 ms per 8192 permutations).  LDS per wavefront here: a 64-record
 // ring per range (a block goes out the moment it is complete, so a ring never holds more than one) + two lane masks per range +
-// the step list of the one-by-one path = 4.9 KB at 16 ranges (64-draw kernel: 10 KB); the jump constants of lane l never change
-// (state l + 1 of every trip) and stay in registers.
+// the step list of the one-by-one path = 4.9 KB at 16 ranges; the jump constants of lane l never change (state l + 1 of every
+// trip) and stay in registers.
 
 __device__ __forceinline__ uint64_t pcgw_draw2(const U128& s, const U128& a, const U128& d, U128& sk) {
     sk = add128(mul128_lo(a, s), d);
@@ -910,261 +583,32 @@ __device__ __forceinline__ void pcgb_copy_out(uint8_t* __restrict__ dst, const u
     }
 }
 
-__global__ __launch_bounds__(PCGB_THREADS) void k_pcg_apply_bucketed(int64_t row_stride, int n_libs, const uint32_t* __restrict__ lib_off,
-                                                                     const uint32_t* __restrict__ lib_phase, const uint8_t* __restrict__ base_pos,
-                                                                     int64_t P, PcgBucketGeom geo, const uint32_t* __restrict__ recs,
-                                                                     const uint32_t* __restrict__ dir, const uint32_t* __restrict__ nblk,
-                                                                     uint8_t* __restrict__ R) {
-    extern __shared__ unsigned char s_dyn[];
-    const uint32_t logS = (uint32_t)geo.logS, S = 1u << logS;
-    uint8_t* const Xw = s_dyn;                                            // the phase's window: positions [f*S, (f+1)*S)
-    uint8_t* const Xr = s_dyn + S;                                        // one range r < f
-    uint32_t* const tags = reinterpret_cast<uint32_t*>(s_dyn + 2 * (size_t)S);  // [2][PCGB_SLOTS]: rounds alternate between the buffers
-    const uint32_t SLOTS = (uint32_t)geo.slots;
-    uint32_t* const blist = tags + 2 * SLOTS;                             // [bcap] block | count << 16, sorted by (range, ordinal)
-    __shared__ uint32_t s_wave_any[2][PCGB_THREADS / 64];                 // per round parity and wave: a record is still pending
-    __shared__ uint32_t s_hist[PCGB_MAX_RANGES], s_start[PCGB_MAX_RANGES + 1];
-    __shared__ uint8_t s_dirty[PCGB_MAX_RANGES];                          // range already written to the row (else: still base_pos)
-    const int tid = threadIdx.x;
-    const uint32_t L = (uint32_t)tid;
-    for (int64_t p = blockIdx.x; p < P; p += gridDim.x) {
-        const uint32_t* const rec_p = recs + (size_t)p * geo.phases * geo.bcap * 64;
-        const uint32_t* const dir_p = dir + (size_t)p * geo.phases * geo.bcap;
-        const uint32_t* const nblk_p = nblk + (size_t)p * geo.phases;
-        uint8_t* const row = R + p * row_stride;
-        for (uint32_t k = L; k < 2 * SLOTS; k += PCGB_THREADS) tags[k] = 0u;
-        uint32_t epoch = 0;
-        for (int l = 0; l < n_libs; ++l) {
-            const uint32_t off = lib_off[l];
-            const uint32_t m = lib_off[l + 1] - off;
-            if (m == 0u) continue;
-            if (m == 1u) {
-                if (tid == 0) row[off] = base_pos[off];
-                continue;
-            }
-            const uint32_t F = (m + S - 1u) >> logS;
-            __syncthreads();
-            if (tid < PCGB_MAX_RANGES) s_dirty[tid] = 0;
-            for (uint32_t ff = F; ff-- > 0u;) {
-                const uint32_t f = ff;
-                const uint32_t ph = lib_phase[l] + f;
-                const uint32_t wlen = min(S, m - (f << logS));
-                __syncthreads();
-                // the conflict tags hold (epoch << 11 | index): epoch restarts with every phase — a phase has at most S / 2048 chunks of
-                // <= 2048 rounds each, far below 2^21, so the epoch field cannot wrap whatever the array length
-                for (uint32_t k = L; k < 2 * SLOTS; k += PCGB_THREADS) tags[k] = 0u;
-                epoch = 0;
-                pcgb_copy_in(Xw, (s_dirty[f] ? row : base_pos) + off + ((size_t)f << logS), wlen, tid);
-                if (tid < PCGB_MAX_RANGES) s_hist[tid] = 0u;
-                __syncthreads();
-                const uint32_t nb = nblk_p[ph];
-                for (uint32_t t = L; t < nb; t += PCGB_THREADS) atomicAdd(&s_hist[dir_p[(size_t)ph * geo.bcap + t] & 0xffu], 1u);
-                __syncthreads();
-                if (tid == 0) {
-                    uint32_t acc = 0;
-                    for (uint32_t r = 0; r <= f; ++r) {
-                        s_start[r] = acc;
-                        acc += s_hist[r];
-                    }
-                    s_start[f + 1] = acc;
-                }
-                __syncthreads();
-                for (uint32_t t = L; t < nb; t += PCGB_THREADS) {
-                    const uint32_t e = dir_p[(size_t)ph * geo.bcap + t];
-                    blist[s_start[e & 0xffu] + (e >> 16)] = t | (((e >> 8) & 0xffu) << 16);
-                }
-                __syncthreads();
-                // Ranges in processing order: rr = 0 is the window range f, rr >= 1 is range rr - 1.  Two software pipelines hide
-                // the global latencies a single resident workgroup cannot overlap otherwise: the records of the NEXT chunk and
-                // the bytes of the NEXT range are loaded into registers while the current chunk runs its rounds.
-                auto range_of = [&](uint32_t rr) { return rr == 0u ? f : rr - 1u; };
-                auto next_range = [&](uint32_t rr) {  // first rr' > rr with records (f + 1: none)
-                    for (++rr; rr <= f && s_hist[range_of(rr)] == 0u; ++rr) {}
-                    return rr;
-                };
-                auto load_recs = [&](uint32_t rr, uint32_t blk0, bool& have) -> uint32_t {  // this wave's block blk0 + wave of range rr
-                    have = false;
-                    if (rr > f) return 0u;
-                    const uint32_t r = range_of(rr), bi = blk0 + (L >> 6);
-                    if (bi >= s_hist[r]) return 0u;
-                    const uint32_t e = blist[s_start[r] + bi];
-                    if ((L & 63u) >= (e >> 16)) return 0u;
-                    have = true;
-                    return rec_p[((size_t)ph * geo.bcap + (e & 0xffffu)) * 64 + (L & 63u)];
-                };
-                uint4 pre0, pre1, pre2, pre3;  // the next range's bytes (16-byte pieces tid, tid + 1024, ...): S <= 65536 = 4 x 1024 x 16
-                pre0 = pre1 = pre2 = pre3 = make_uint4(0u, 0u, 0u, 0u);
-                auto range_src = [&](uint32_t rr) { return (s_dirty[range_of(rr)] ? row : base_pos) + off + ((size_t)range_of(rr) << logS); };
-                const uint32_t n16 = S >> 4;
-                // only whole, 16-byte aligned ranges are prefetched (else: plain copy at the switch)
-#define SQGR_PCGB_PREFETCH(RR, OK)                                                                            \
-    do {                                                                                                      \
-        OK = false;                                                                                           \
-        const uint32_t rr__ = (RR);                                                                           \
-        if (rr__ <= f && rr__ != 0u && S >= 16u) {                                                            \
-            const uint4* src__ = reinterpret_cast<const uint4*>(range_src(rr__));                             \
-            if ((reinterpret_cast<uintptr_t>(src__) & 15u) == 0u) {                                           \
-                if ((uint32_t)tid < n16) pre0 = src__[tid];                                                   \
-                if ((uint32_t)tid + 1024u < n16) pre1 = src__[tid + 1024];                                    \
-                if ((uint32_t)tid + 2048u < n16) pre2 = src__[tid + 2048];                                    \
-                if ((uint32_t)tid + 3072u < n16) pre3 = src__[tid + 3072];                                    \
-                OK = true;                                                                                    \
-            }                                                                                                 \
-        }                                                                                                     \
-    } while (0)
-                uint32_t rr = s_hist[f] != 0u ? 0u : next_range(0u), c0 = 0;
-                // a chunk = 32 blocks in time order: lane L of the workgroup holds record L (blocks c0 .. c0+15) and record 1024 + L
-                // (blocks c0+16 .. c0+31)
-                bool have_a = false, have_b = false;
-                uint32_t rec_a = load_recs(rr, c0, have_a), rec_b = load_recs(rr, c0 + 16u, have_b);
-                bool pre_ok = false;
-                while (rr <= f) {
-                    const uint32_t r = range_of(rr), nbr = s_hist[r];
-                    const bool internal = rr == 0u;
-                    uint8_t* const X2 = internal ? Xw : Xr;
-                    // the chunk after this one: next chunk of the range, or the first chunk of the next range with records
-                    const bool last_chunk = c0 + PCGB_CHUNK_BLOCKS >= nbr;
-                    const uint32_t rr_n = last_chunk ? next_range(rr) : rr, c0_n = last_chunk ? 0u : c0 + PCGB_CHUNK_BLOCKS;
-                    if (c0 == 0u) {  // entering range r
-                        if (!internal) {
-                            if (pre_ok) {
-                                uint4* dst = reinterpret_cast<uint4*>(Xr);
-                                if ((uint32_t)tid < n16) dst[tid] = pre0;
-                                if ((uint32_t)tid + 1024u < n16) dst[tid + 1024] = pre1;
-                                if ((uint32_t)tid + 2048u < n16) dst[tid + 2048] = pre2;
-                                if ((uint32_t)tid + 3072u < n16) dst[tid + 3072] = pre3;
-                            } else {
-                                pcgb_copy_in(Xr, range_src(rr), S, tid);
-                            }
-                            __syncthreads();
-                        }
-                        SQGR_PCGB_PREFETCH(next_range(rr), pre_ok);  // in flight while this range is replayed
-                    }
-                    bool have_na = false, have_nb = false;
-                    const uint32_t rec_na = load_recs(rr_n, c0_n, have_na), rec_nb = load_recs(rr_n, c0_n + 16u, have_nb);
-                    bool pend_a = have_a, pend_b = have_b;
-                    const uint32_t ja = rec_a & 0xffffu, ia = rec_a >> 16, jb = rec_b & 0xffffu, ib = rec_b >> 16;
-                    const uint32_t hja = __umulhi(ja * 2654435761u, SLOTS), hia = __umulhi(ia * 2654435761u, SLOTS);
-                    const uint32_t hjb = __umulhi(jb * 2654435761u, SLOTS), hib = __umulhi(ib * 2654435761u, SLOTS);
-                    // ONE barrier per round: the tags of consecutive rounds live in different buffers (a fast wave's claims of round
-                    // k + 1 cannot disturb a slow wave still reading round k; the barrier of round k + 1 protects the buffer's
-                    // re-use in round k + 2), and so do the per-wave "still pending" words.  Tag = epoch | 2047 - index in the chunk.
-                    // (Measured alternatives, all slower on MI355X: compacting the records the first round leaves onto the first
-                    // waves — one more barrier and an LDS queue per chunk, 91 ms instead of 75 ms per 8192 permutations of 1e6
-                    // positions; a branch-free round with per-lane dummy slots instead of masked lanes — 95 instructions per round
-                    // instead of ~160, but every lane then issues every LDS operation of every round: 94 ms.)
-                    for (;;) {
-                        ++epoch;
-                        uint32_t* const T = tags + (epoch & 1u) * SLOTS;
-                        const uint32_t mine_a = (epoch << 11) | (2047u - L), mine_b = (epoch << 11) | (1023u - L);
-                        if (pend_a) atomicMax(&T[hja], mine_a);
-                        if (pend_b) atomicMax(&T[hjb], mine_b);
-                        const bool wave_pending = __ballot(pend_a || pend_b) != 0ull;
-                        if ((L & 63u) == 0u) s_wave_any[epoch & 1u][L >> 6] = wave_pending ? 1u : 0u;
-                        __syncthreads();
-                        const uint32_t wa = s_wave_any[epoch & 1u][L & (PCGB_THREADS / 64 - 1)];
-                        // (every LDS read of a round is issued only by the lanes, and in the ranges, that need it: -2.7 %)
-                        uint32_t ta = 0, tb = 0, tia = 0, tib = 0;
-                        uint8_t va_i = 0, va_j = 0;
-                        if (pend_a) {
-                            ta = T[hja];
-                            va_i = Xw[ia];
-                            va_j = X2[ja];
-                        }
-                        if (pend_b) tb = T[hjb];
-                        if (internal) {
-                            if (pend_a) tia = T[hia];
-                            if (pend_b) tib = T[hib];
-                        }
-                        if (__ballot(wa != 0u) == 0ull) break;  // uniform over the workgroup: every wave reads all 16 words
-                        bool go_a = pend_a && ta == mine_a, go_b = pend_b && tb == mine_b;
-                        // window range: no earlier pending record of the chunk may write to this record's i position
-                        if (internal) {
-                            go_a = go_a && ((tia >> 11) != epoch || (2047u - (tia & 2047u)) >= L);
-                            go_b = go_b && ((tib >> 11) != epoch || (2047u - (tib & 2047u)) >= 1024u + L);
-                        }
-                        if (go_a) {
-                            Xw[ia] = va_j;
-                            X2[ja] = va_i;
-                            pend_a = false;
-                        }
-                        if (go_b) {  // after this lane's own record a (had a been blocked on a shared position, so would b be)
-                            const uint8_t vb_i = Xw[ib], vb_j = X2[jb];
-                            Xw[ib] = vb_j;
-                            X2[jb] = vb_i;
-                            pend_b = false;
-                        }
-                    }
-                    if (last_chunk && !internal) {
-                        __syncthreads();
-                        pcgb_copy_out(row + off + ((size_t)r << logS), Xr, S, tid);
-                        if (tid == 0) s_dirty[r] = 1;
-                        __syncthreads();
-                    }
-                    rr = rr_n;
-                    c0 = c0_n;
-                    rec_a = rec_na;
-                    rec_b = rec_nb;
-                    have_a = have_na;
-                    have_b = have_nb;
-                }
-#undef SQGR_PCGB_PREFETCH
-                pcgb_copy_out(row + off + ((size_t)f << logS), Xw, wlen, tid);  // positions of this phase are final
-            }
-        }
-        __syncthreads();
-    }
-}
-
 // ---- the replay with exact claims (round 6): bitmaps instead of hashed tags, contested records deferred ------------------
-// k_pcg_apply_bucketed's rounds are spent on FALSE conflicts: 2048 records claim 3328 hashed tag slots, 46 % lose the first round
-// to a record with another position, ~4.4 barrier rounds per chunk — while only 3-6 % of a chunk's records really share a
-// position with another record of the chunk.  This kernel claims positions EXACTLY, one bit per position of the window (8 KB):
+// Only 3-6 % of a chunk's 2048 records really share a position with another record of the chunk.  (The replay of rounds 4-5 let
+// every record claim one of 3328 hashed tag slots in barrier rounds: 46 % lost the first round to a record with another position,
+// ~4.4 rounds per chunk.  Retired: DESIGN.md §4.)  This kernel claims positions EXACTLY, one bit per position of the window (8 KB):
 //   claim   every record ORs the bit(s) of its position(s) into the claim bitmap A (ds_or_rtn); a record that finds a bit already
 //           set knows it is contested and sets the bit(s) in the poison bitmap B — which also tells the first arriver;
 //   apply   (behind a barrier) a record with none of its positions in B swaps at once — it is the only record of the chunk on
 //           them and every earlier record on them has gone; the others are DEFERRED: appended to a queue in LDS with their
 //           time index (chunk << 11 | slot), their positions stay poisoned, so later records that touch them queue up behind
 //           them (a queued record and a later unqueued one never share a position: they commute);
-//   drain   when the list ends (the range's bytes leave LDS) or the queue is half full: the queued records go in the priority
-//           rounds of the old kernel (hashed tags, atomic max of epoch | earliest time index, the i-side rule of the window
-//           range) — a few hundred records on 2 x 1024 slots (they alias the claim bitmap, which is all zero between chunks);
+//   drain   when the list ends (the range's bytes leave LDS) or the queue is half full: the queued records go in priority
+//           rounds, one barrier each (hashed tags, atomic max of epoch | earliest time index: a record goes when it is the
+//           earliest pending one on its j slot and, in the window range, no earlier one writes to its i position) — a few hundred records on 2 x 1024 slots (they alias the claim bitmap, which is all zero between chunks);
 //           each clears its words of B.
 // A chunk costs two barrier intervals instead of ~4.4 rounds, a list one drain of ~4-6 rounds.  A record that finds the queue
 // full stays with its lane and joins the drain that follows at once (slots a / b of the drain: robust for any stream).
 constexpr int PCGQ_CAP = 1024;     // queue entries (4 + 2 bytes each)
 constexpr int PCGQ_SLOTS = 1024;   // conflict tags per buffer of a drain (two buffers = the 8 KB of the claim bitmap at S = 65536)
 constexpr int PCGQ_TAG_BYTES = 2 * PCGQ_SLOTS * 4;
-#ifndef SQGR_PCGQ_NSUB
-#define SQGR_PCGQ_NSUB 2
-#endif
-constexpr int PCGQ_NSUB = SQGR_PCGQ_NSUB;  // chunks per super-chunk of record loads
+constexpr int PCGQ_NSUB = 2;       // chunks per super-chunk of record loads
 
 __host__ __device__ inline uint32_t pcgq_bitmap_bytes(uint32_t S) { return S / 8u < 16u ? 16u : S / 8u; }
 __host__ __device__ inline uint32_t pcgq_claim_bytes(uint32_t S) { return pcgq_bitmap_bytes(S) < (uint32_t)PCGQ_TAG_BYTES ? (uint32_t)PCGQ_TAG_BYTES : pcgq_bitmap_bytes(S); }
 static size_t pcgq_lds_bytes(uint32_t S, int bcap) {
     return 2 * (size_t)S + pcgq_claim_bytes(S) + pcgq_bitmap_bytes(S) + (size_t)PCGQ_CAP * 6 + (size_t)bcap * 4;
 }
-
-#ifdef SQGR_PCG_PROFILE
-// developer build (tools/pcg_profile.sh): shader-clock time per section, counts of chunks / drains / drain rounds / queued records
-__device__ unsigned long long g_pcgq_prof[16];
-#define PCGQ_T0() unsigned long long t0__ = __builtin_amdgcn_s_memtime()
-#define PCGQ_ACC(SLOT)                                                          \
-    do {                                                                        \
-        const unsigned long long t1__ = __builtin_amdgcn_s_memtime();           \
-        if (tid == 0) atomicAdd(&g_pcgq_prof[SLOT], t1__ - t0__);               \
-        t0__ = t1__;                                                            \
-    } while (0)
-#define PCGQ_CNT(SLOT, V)                                                       \
-    do {                                                                        \
-        if (tid == 0) atomicAdd(&g_pcgq_prof[SLOT], (unsigned long long)(V));   \
-    } while (0)
-#else
-#define PCGQ_T0() do {} while (0)
-#define PCGQ_ACC(SLOT) do {} while (0)
-#define PCGQ_CNT(SLOT, V) do {} while (0)
-#endif
 
 __global__ __launch_bounds__(PCGB_THREADS) void k_pcg_apply_claims(int64_t row_stride, int n_libs, const uint32_t* __restrict__ lib_off,
                                                                    const uint32_t* __restrict__ lib_phase, const uint8_t* __restrict__ base_pos,
@@ -1215,7 +659,6 @@ __global__ __launch_bounds__(PCGB_THREADS) void k_pcg_apply_claims(int64_t row_s
                 const uint32_t ph = lib_phase[l] + f;
                 const uint32_t wlen = min(S, m - (f << logS));
                 __syncthreads();
-                PCGQ_T0();
                 pcgb_copy_in(Xw, (s_dirty[f] ? row : base_pos) + off + ((size_t)f << logS), wlen, tid);
                 if (tid < PCGB_MAX_RANGES) s_hist[tid] = 0u;
                 __syncthreads();
@@ -1236,7 +679,10 @@ __global__ __launch_bounds__(PCGB_THREADS) void k_pcg_apply_claims(int64_t row_s
                     blist[s_start[e & 0xffu] + (e >> 16)] = t | (((e >> 8) & 0xffu) << 16);
                 }
                 __syncthreads();
-                // (range order, the two software pipelines — next chunk's records, next range's bytes — as in k_pcg_apply_bucketed)
+                // Ranges in processing order: rr = 0 is the window range f, rr >= 1 is range rr - 1.  Two software pipelines hide
+                // the global latencies a single resident workgroup cannot overlap otherwise: the records of the NEXT super-chunk and
+                // the bytes of the NEXT range (whole, 16-byte aligned ranges only; else a plain copy at the switch) are loaded into
+                // registers while the current chunks are replayed.
                 auto range_of = [&](uint32_t rr) { return rr == 0u ? f : rr - 1u; };
                 auto next_range = [&](uint32_t rr) {
                     for (++rr; rr <= f && s_hist[range_of(rr)] == 0u; ++rr) {}
@@ -1263,8 +709,8 @@ __global__ __launch_bounds__(PCGB_THREADS) void k_pcg_apply_claims(int64_t row_s
     } while (0)
                 // The records of a list are loaded a SUPER-CHUNK (PCGQ_NSUB chunks) at a time, the next super-chunk's loads issued
                 // right behind the wait for this one's: a chunk is two short barrier intervals, far less than an HBM round trip, and
-                // the compiler's wait for conditionally issued loads is vmcnt(0) — with one chunk in flight per wait (the shape of
-                // k_pcg_apply_bucketed) every chunk paid the whole latency.
+                // the compiler's wait for conditionally issued loads is vmcnt(0) — with one chunk in flight per wait every
+                // chunk paid the whole latency.
                 uint32_t rr = s_hist[f] != 0u ? 0u : next_range(0u), c0 = 0;
                 auto load_super = [&](uint32_t rrx, uint32_t s0, uint32_t (&out)[2 * PCGQ_NSUB], uint32_t& hv) {
                     hv = 0u;
@@ -1285,7 +731,6 @@ __global__ __launch_bounds__(PCGB_THREADS) void k_pcg_apply_claims(int64_t row_s
                 };
                 uint32_t cur[2 * PCGQ_NSUB], nxt[2 * PCGQ_NSUB], cur_hv = 0u, nxt_hv = 0u;
                 load_super(rr, c0, cur, cur_hv);
-                PCGQ_ACC(0);
                 bool pre_ok = false;
                 uint32_t seq = 0;  // chunks since the last drain (5 bits of the time index)
                 while (rr <= f) {
@@ -1295,11 +740,7 @@ __global__ __launch_bounds__(PCGB_THREADS) void k_pcg_apply_claims(int64_t row_s
                     const bool last_super = c0 + PCGQ_NSUB * PCGB_CHUNK_BLOCKS >= nbr;
                     const uint32_t rr_n = last_super ? next_range(rr) : rr, c0_n = last_super ? 0u : c0 + PCGQ_NSUB * PCGB_CHUNK_BLOCKS;
                     if (c0 == 0u) {  // entering range r
-#if defined(SQGR_PCG_ABLATE) && (SQGR_PCG_ABLATE & 2)
-                        if (false) {
-#else
                         if (!internal) {
-#endif
                             if (pre_ok) {
                                 uint4* dst = reinterpret_cast<uint4*>(Xr);
                                 if ((uint32_t)tid < n16) dst[tid] = pre0;
@@ -1310,10 +751,7 @@ __global__ __launch_bounds__(PCGB_THREADS) void k_pcg_apply_claims(int64_t row_s
                                 pcgb_copy_in(Xr, range_src(rr), S, tid);
                             }
                         }
-#if !(defined(SQGR_PCG_ABLATE) && (SQGR_PCG_ABLATE & 2))
                         SQGR_PCGQ_PREFETCH(next_range(rr), pre_ok);  // in flight while this range is replayed
-#endif
-                        PCGQ_ACC(1);
                     }
                     // touch this super-chunk's records (the wait lands here), then put the next one's loads in flight
                     {
@@ -1322,20 +760,14 @@ __global__ __launch_bounds__(PCGB_THREADS) void k_pcg_apply_claims(int64_t row_s
                         for (int q = 0; q < 2 * PCGQ_NSUB; ++q) acc |= cur[q];
                         asm volatile("" ::"v"(acc));
                     }
-                    PCGQ_ACC(12);
                     load_super(rr_n, c0_n, nxt, nxt_hv);
-                    PCGQ_ACC(13);
                     // (INTERNAL_C: the window range — both sides of a record in Xw — as a compile-time constant: the other ranges, four
                     // records in five, run without its branches)
                     auto chunk = [&](auto INTERNAL_C, const uint32_t rec_a, const uint32_t rec_b, const bool have_a, const bool have_b, const bool last_chunk) {
                         constexpr bool internal = decltype(INTERNAL_C)::value;
                         const uint32_t ja = rec_a & 0xffffu, ia = rec_a >> 16, jb = rec_b & 0xffffu, ib = rec_b >> 16;
                         // a swap of a position with itself changes nothing and claims nothing
-#if defined(SQGR_PCG_ABLATE) && (SQGR_PCG_ABLATE & 4)  // timing experiment (wrong results): no record claims or swaps anything
-                        const bool act_a = have_a && ia == 0x12345u, act_b = have_b && ib == 0x12345u;
-#else
                         const bool act_a = have_a && !(internal && ia == ja), act_b = have_b && !(internal && ib == jb);
-#endif
                         const uint32_t wja = ja >> 5, bja = 1u << (ja & 31u), wia = ia >> 5, bia = 1u << (ia & 31u);
                         const uint32_t wjb = jb >> 5, bjb = 1u << (jb & 31u), wib = ib >> 5, bib = 1u << (ib & 31u);
                         // ---- claim
@@ -1360,8 +792,6 @@ __global__ __launch_bounds__(PCGB_THREADS) void k_pcg_apply_claims(int64_t row_s
                             }
                         }
                         __syncthreads();  // (also: the range's bytes stored above are in place)
-                        PCGQ_ACC(2);
-                        PCGQ_CNT(8, 1);
                         // ---- apply or defer
                         bool def_a = false, def_b = false;
                         // (measured and dropped: the claims, poison look-ups and clears issued by every lane without branches —
@@ -1427,7 +857,6 @@ __global__ __launch_bounds__(PCGB_THREADS) void k_pcg_apply_claims(int64_t row_s
                             }
                         }
                         __syncthreads();
-                        PCGQ_ACC(3);
                         const uint32_t qc = s_qcount;
                         const bool spill = s_spill != 0u;
                         ++seq;
@@ -1436,8 +865,6 @@ __global__ __launch_bounds__(PCGB_THREADS) void k_pcg_apply_claims(int64_t row_s
                         } else if (last_chunk || qc > qcap / 2u || spill || seq == 32u) {
                             // ---- drain: the queued records (lane L: entry L) and the spilled ones in priority rounds
                             const uint32_t nq = min(qc, qcap);
-                            PCGQ_CNT(9, 1);
-                            PCGQ_CNT(11, qc);
                             const bool was_q = L < nq;
                             const uint32_t rec_q = was_q ? Qrec[L] : 0u;
                             const uint32_t prio_q = was_q ? (uint32_t)Qprio[L] : 0u;
@@ -1448,21 +875,6 @@ __global__ __launch_bounds__(PCGB_THREADS) void k_pcg_apply_claims(int64_t row_s
                             bool pend_q = was_q, pend_a = sp_a, pend_b = sp_b;
                             const bool any_sp = spill;  // uniform over the workgroup
                             uint32_t ep = 0;
-#if defined(SQGR_PCG_ABLATE) && (SQGR_PCG_ABLATE & 1)  // timing experiment (wrong results): the drain without its rounds
-                            if (pend_q) {
-                                Bm[jq >> 5] = 0u;
-                                if (internal) Bm[iq >> 5] = 0u;
-                            }
-                            if (pend_a) {
-                                Bm[wja] = 0u;
-                                if (internal) Bm[wia] = 0u;
-                            }
-                            if (pend_b) {
-                                Bm[wjb] = 0u;
-                                if (internal) Bm[wib] = 0u;
-                            }
-                            pend_q = pend_a = pend_b = false;
-#endif
                             // wavefronts without a record (lane L holds queue entry L: all but the first few) only keep the barriers
                             // company — out of the way of the SIMDs' instruction issue
                             if ((L & ~63u) >= nq && !any_sp) {
@@ -1476,7 +888,6 @@ __global__ __launch_bounds__(PCGB_THREADS) void k_pcg_apply_claims(int64_t row_s
                             } else
                             for (;;) {
                                 ++ep;
-                                PCGQ_CNT(10, 1);
                                 uint32_t* const T = A + (ep & 1u) * PCGQ_SLOTS;
                                 const uint32_t mine_q = (ep << 16) | (0xffffu - prio_q);
                                 const uint32_t mine_a = (ep << 16) | (0xffffu - prio_a), mine_b = (ep << 16) | (0xffffu - prio_b);
@@ -1549,7 +960,6 @@ __global__ __launch_bounds__(PCGB_THREADS) void k_pcg_apply_claims(int64_t row_s
                             }
                             seq = 0;
                             __syncthreads();
-                            PCGQ_ACC(4);
                         }
                     };
 #pragma unroll
@@ -1563,12 +973,9 @@ __global__ __launch_bounds__(PCGB_THREADS) void k_pcg_apply_claims(int64_t row_s
                                   c0 + (uint32_t)(t + 1) * PCGB_CHUNK_BLOCKS >= nbr);
                     }
                     if (last_super && !internal) {
-#if !(defined(SQGR_PCG_ABLATE) && (SQGR_PCG_ABLATE & 2))  // timing experiment (wrong results): ranges neither loaded nor stored
                         pcgb_copy_out(row + off + ((size_t)r << logS), Xr, S, tid);
-#endif
                         if (tid == 0) s_dirty[r] = 1;
                         __syncthreads();
-                        PCGQ_ACC(5);
                     }
                     rr = rr_n;
                     c0 = c0_n;
@@ -1578,7 +985,6 @@ __global__ __launch_bounds__(PCGB_THREADS) void k_pcg_apply_claims(int64_t row_s
                 }
 #undef SQGR_PCGQ_PREFETCH
                 pcgb_copy_out(row + off + ((size_t)f << logS), Xw, wlen, tid);  // positions of this phase are final
-                PCGQ_ACC(6);
             }
         }
         __syncthreads();
@@ -1597,19 +1003,6 @@ __global__ __launch_bounds__(256) void k_rows_to_columns_u8(int64_t n, int64_t r
     // must never see stale bytes there (a stale value >= K would index outside the count kernel's counters)
     for (int r = ty; r < 64; r += 4)
         if (e0 + r < n && q0 + tx < stride) W[(e0 + r) * stride + q0 + tx] = tile[tx][r];
-}
-
-// idx[p][i] = W[i][p]  (autocorr row permutations)
-__global__ __launch_bounds__(256) void k_columns_to_rows_i32(int64_t n, int64_t stride, const int32_t* __restrict__ W, int64_t P,
-                                                             int32_t* __restrict__ idx) {
-    __shared__ int32_t tile[32][33];
-    const int64_t i0 = (int64_t)blockIdx.x * 32, q0 = (int64_t)blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int r = ty; r < 32; r += 8)
-        tile[r][tx] = (i0 + r < n && q0 + tx < P) ? W[(i0 + r) * stride + q0 + tx] : 0;
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8)
-        if (q0 + r < P && i0 + tx < n) idx[(size_t)(q0 + r) * n + i0 + tx] = tile[tx][r];
 }
 
 }  // namespace sqgr
@@ -1636,15 +1029,6 @@ static int ensure_pcg_jump(DevBuf<uint64_t>& buf) {
     return SQGR_OK;
 }
 
-static bool pcg_lane_kernel() {  // SQGR_PCG_KERNEL=lane selects the one-thread-per-permutation kernel (comparison runs)
-    const char* e = getenv("SQGR_PCG_KERNEL");
-    return e && strcmp(e, "lane") == 0;
-}
-static unsigned pcg_grid(int64_t pc) {  // SQGR_PCG_WAVES caps the number of permutations in flight (tuning runs)
-    const char* e = getenv("SQGR_PCG_WAVES");
-    const int64_t cap = (e && atoll(e) > 0) ? atoll(e) : pc;
-    return (unsigned)std::min<int64_t>(pc, cap);
-}
 // LDS window (elements, power of two).  Measured on MI355X: a larger window (up to the whole array) buys nothing — the
 // trips are bound by their own instruction stream, not by the i-side loads — and costs occupancy.
 static uint32_t pcg_window(int64_t n_max) {
@@ -1665,9 +1049,9 @@ static int pcg_force_slow() {
 
 namespace sqgr {
 
-// The bucketed replay (k_pcg_draws_bucketed + k_pcg_apply_bucketed) is chosen for long arrays, where the wave kernel's rows fall
-// out of every cache; SQGR_PCG_KERNEL=bucket|wave|lane forces a kernel, SQGR_PCG_BUCKET_LOGS the phase length (tests: many phases
-// on small arrays).
+// The bucketed replay (k_pcg_draws_bucketed2 + k_pcg_apply_claims) is chosen for long arrays, where the wave kernel's rows fall
+// out of every cache; SQGR_PCG_KERNEL=bucket|wave forces a path, SQGR_PCG_BUCKET_LOGS the phase length (tests: many phases on
+// small arrays).
 static int pcg_bucket_logs(int64_t n_lib_max) {
     const char* e = getenv("SQGR_PCG_BUCKET_LOGS");
     int logs = (e && atoi(e) >= 6 && atoi(e) <= 16) ? atoi(e) : 16;
@@ -1677,7 +1061,7 @@ static int pcg_bucket_logs(int64_t n_lib_max) {
 static bool pcg_use_bucket(int64_t n, int64_t n_lib_max) {
     const char* e = getenv("SQGR_PCG_KERNEL");
     if (e && strcmp(e, "bucket") == 0) return ceil_div(n_lib_max, (int64_t)1 << pcg_bucket_logs(n_lib_max)) <= PCGB_MAX_RANGES;
-    if (e && (strcmp(e, "wave") == 0 || strcmp(e, "lane") == 0)) return false;
+    if (e && strcmp(e, "wave") == 0) return false;
     // (round 6, tools/pcg_threshold_time.py: with the 128-draw generator and the claims replay the pipeline wins from ~65 000
     // positions on — 1e5 positions x 10 000 permutations 17.5 ms against the wave kernel's 23.9, 80 000: 15.5 / 18.1, 40 000: 4.5 / 4.5)
     return n >= ((int64_t)1 << 16) && ceil_div(n_lib_max, (int64_t)1 << 16) <= PCGB_MAX_RANGES;
@@ -1725,30 +1109,12 @@ static int pcg_shuffle_rows_bucketed(sqgr_ctx* ctx, PcgWorkspace& ws, int64_t n,
     SQGR_TRY(ws.recs.ensure((size_t)sub * rec_words));
     SQGR_TRY(ws.dir.ensure((size_t)sub * geo.phases * geo.bcap));
     SQGR_TRY(ws.nblk.ensure((size_t)sub * geo.phases));
-    // generator: 128 draws per trip (default), or rounds 4-5's 64 (SQGR_PCG_DRAWS=64)
-    const char* draws_env = getenv("SQGR_PCG_DRAWS");
-    const bool draws128 = !(draws_env && atoi(draws_env) == 64);
-    size_t lds_g = draws128 ? pcg_draws2_lds_bytes(geo.n_ranges) : (size_t)geo.n_ranges * PCGB_RING * 4;
-    if (const char* e = getenv("SQGR_PCG_LDS_PAD")) lds_g += (size_t)atoi(e);  // occupancy experiments
-    // conflict tags: what the two windows and the block list leave of the LDS (SQGR_PCG_BUCKET_SLOTS: experiments), at least 3328
-    {
-        const int64_t room = ((int64_t)160 << 10) - 2 * S - (int64_t)geo.bcap * 4 - 2048;  // (2 KB: the kernel's static LDS)
-        int64_t slots = std::max<int64_t>(PCGB_SLOTS, std::min<int64_t>(room / 8, 16384));
-        if (const char* e = getenv("SQGR_PCG_BUCKET_SLOTS"))
-            if (atoi(e) >= 64) slots = std::min<int64_t>(atoi(e), std::max<int64_t>(room / 8, PCGB_SLOTS));
-        geo.slots = (int)slots;
-    }
-    // replay kernel: exact claims + deferred queue (default), or rounds 4-5's hashed tags (SQGR_PCG_APPLY=tags)
     geo.qcap = PCGQ_CAP;
     if (const char* e = getenv("SQGR_PCG_QUEUE_CAP"))
         if (atoi(e) >= 2 && atoi(e) <= PCGQ_CAP) geo.qcap = atoi(e);
-    const char* apply_env = getenv("SQGR_PCG_APPLY");  // (read at every call: tools/pcg_bucket_time.py compares the two)
-    const bool use_claims = !(apply_env && strcmp(apply_env, "tags") == 0);
-    const size_t lds_a = use_claims ? pcgq_lds_bytes((uint32_t)S, geo.bcap) : 2 * (size_t)S + (size_t)2 * geo.slots * 4 + (size_t)geo.bcap * 4;
-    if (draws128) SQGR_TRY(pcg_allow_lds(k_pcg_draws_bucketed2, lds_g));
-    else SQGR_TRY(pcg_allow_lds(k_pcg_draws_bucketed, lds_g));
-    if (use_claims) SQGR_TRY(pcg_allow_lds(k_pcg_apply_claims, lds_a));
-    else SQGR_TRY(pcg_allow_lds(k_pcg_apply_bucketed, lds_a));
+    const size_t lds_g = pcg_draws2_lds_bytes(geo.n_ranges), lds_a = pcgq_lds_bytes((uint32_t)S, geo.bcap);
+    SQGR_TRY(pcg_allow_lds(k_pcg_draws_bucketed2, lds_g));
+    SQGR_TRY(pcg_allow_lds(k_pcg_apply_claims, lds_a));
     const std::string name_g = std::string(timer_name) + "_draws", name_a = std::string(timer_name) + "_apply";
     const int cus = std::max(ctx->cu_count, 1);
     const int wg_per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, ((size_t)160 << 10) / (lds_a + 1024)));
@@ -1757,38 +1123,15 @@ static int pcg_shuffle_rows_bucketed(sqgr_ctx* ctx, PcgWorkspace& ws, int64_t n,
         SQGR_HIP(hipMemsetAsync(ws.nblk.p, 0, (size_t)qc * geo.phases * 4, st));
         {
             LaunchTimer t(ctx, name_g.c_str(), st);
-            if (draws128)
-                k_pcg_draws_bucketed2<<<(unsigned)qc, 64, lds_g, st>>>(n_libs, lib_off_dev, ws.lib_phase.p, states_dev + 4 * q0, ws.jump.p, qc, geo,
-                                                                       ws.recs.p, ws.dir.p, ws.nblk.p, pcg_force_slow());
-            else
-                k_pcg_draws_bucketed<<<(unsigned)qc, 64, lds_g, st>>>(n_libs, lib_off_dev, ws.lib_phase.p, states_dev + 4 * q0, ws.jump.p, qc, geo, ws.recs.p,
-                                                                      ws.dir.p, ws.nblk.p, pcg_force_slow());
+            k_pcg_draws_bucketed2<<<(unsigned)qc, 64, lds_g, st>>>(n_libs, lib_off_dev, ws.lib_phase.p, states_dev + 4 * q0, ws.jump.p, qc, geo, ws.recs.p,
+                                                                   ws.dir.p, ws.nblk.p, pcg_force_slow());
             SQGR_HIP(hipGetLastError());
         }
         {
             LaunchTimer t(ctx, name_a.c_str(), st);
             const unsigned grid = (unsigned)std::min<int64_t>(qc, (int64_t)cus * wg_per_cu);
-            if (use_claims) {
-#ifdef SQGR_PCG_PROFILE
-                unsigned long long zero[16] = {0};
-                SQGR_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_pcgq_prof), zero, sizeof zero));
-#endif
-                k_pcg_apply_claims<<<grid, PCGB_THREADS, lds_a, st>>>(n_pad, n_libs, lib_off_dev, ws.lib_phase.p, base_pos_dev, qc, geo, ws.recs.p, ws.dir.p,
-                                                                      ws.nblk.p, ws.rows.p + (size_t)q0 * n_pad);
-#ifdef SQGR_PCG_PROFILE
-                unsigned long long prof[16];
-                SQGR_HIP(hipStreamSynchronize(st));
-                SQGR_HIP(hipMemcpyFromSymbol(prof, HIP_SYMBOL(g_pcgq_prof), sizeof prof));
-                fprintf(stderr, "pcgq profile (%lld permutations; shader clocks per permutation): phase setup %.0f, range entry %.0f, record wait %.0f, "
-                        "record issue %.0f, claim %.0f, apply %.0f, drain %.0f, range out %.0f, window out %.0f | per permutation: chunks %.1f, drains %.1f, "
-                        "drain rounds %.1f, queued %.1f\n", (long long)qc, prof[0] / (double)qc, prof[1] / (double)qc, prof[12] / (double)qc,
-                        prof[13] / (double)qc, prof[2] / (double)qc, prof[3] / (double)qc, prof[4] / (double)qc, prof[5] / (double)qc, prof[6] / (double)qc,
-                        prof[8] / (double)qc, prof[9] / (double)qc, prof[10] / (double)qc, prof[11] / (double)qc);
-#endif
-            }
-            else
-                k_pcg_apply_bucketed<<<grid, PCGB_THREADS, lds_a, st>>>(n_pad, n_libs, lib_off_dev, ws.lib_phase.p, base_pos_dev, qc, geo, ws.recs.p, ws.dir.p,
-                                                                        ws.nblk.p, ws.rows.p + (size_t)q0 * n_pad);
+            k_pcg_apply_claims<<<grid, PCGB_THREADS, lds_a, st>>>(n_pad, n_libs, lib_off_dev, ws.lib_phase.p, base_pos_dev, qc, geo, ws.recs.p, ws.dir.p,
+                                                                  ws.nblk.p, ws.rows.p + (size_t)q0 * n_pad);
             SQGR_HIP(hipGetLastError());
         }
     }
@@ -1796,14 +1139,8 @@ static int pcg_shuffle_rows_bucketed(sqgr_ctx* ctx, PcgWorkspace& ws, int64_t n,
     return SQGR_OK;
 }
 
-bool pcg_rows_available() { return !pcg_lane_kernel(); }
-
 int pcg_shuffle_rows(sqgr_ctx* ctx, PcgWorkspace& ws, int64_t n, int n_libs, const uint32_t* lib_off_dev, const uint8_t* base_pos_dev,
                      const uint64_t* states_dev, int64_t pc, hipStream_t st, const char* timer_name, int64_t* row_stride) {
-    if (pcg_lane_kernel()) {
-        set_error("SQGR_PCG_KERNEL=lane shuffles columns, not rows");
-        return SQGR_ERR_UNSUPPORTED;
-    }
     const int64_t n_pad = ceil_div(n, 64) * 64;
     *row_stride = n_pad;
     SQGR_TRY(ensure_pcg_jump(ws.jump));
@@ -1832,7 +1169,7 @@ int pcg_shuffle_rows(sqgr_ctx* ctx, PcgWorkspace& ws, int64_t n, int n_libs, con
         LaunchTimer t(ctx, timer_name, st);
         const uint32_t wsz = pcg_window(n);
         SQGR_TRY(pcg_allow_lds(k_pcg_shuffle_wave<uint8_t, false>, (size_t)wsz));
-        k_pcg_shuffle_wave<uint8_t, false><<<pcg_grid(pc), 64, (size_t)wsz, st>>>(n, n_pad, n_libs, lib_off_dev, base_pos_dev, states_dev,
+        k_pcg_shuffle_wave<uint8_t, false><<<(unsigned)pc, 64, (size_t)wsz, st>>>(n, n_pad, n_libs, lib_off_dev, base_pos_dev, states_dev,
                                                                                   ws.jump.p, pc, ws.rows.p, pcg_force_slow(), wsz);
         SQGR_HIP(hipGetLastError());
     }
@@ -1841,15 +1178,6 @@ int pcg_shuffle_rows(sqgr_ctx* ctx, PcgWorkspace& ws, int64_t n, int n_libs, con
 
 int pcg_shuffle_labels(sqgr_ctx* ctx, PcgWorkspace& ws, int64_t n, int n_libs, const uint32_t* lib_off_dev, const uint8_t* base_pos_dev,
                        const uint64_t* states_dev, int64_t pc, int64_t stride, uint8_t* W, hipStream_t st, const char* timer_name) {
-    if (pcg_lane_kernel()) {
-        LaunchTimer t(ctx, timer_name, st);
-        const int64_t pc64 = std::min<int64_t>(stride, ceil_div(pc, 64) * 64);
-        if (pc64 > pc)  // columns past pc that whole-batch consumers still read: label 0 instead of stale bytes
-            SQGR_HIP(hipMemset2DAsync(W + pc, (size_t)stride, 0, (size_t)(pc64 - pc), (size_t)n, st));
-        k_pcg_shuffle<uint8_t, false><<<(unsigned)ceil_div(pc, 64), 64, 0, st>>>(n, n_libs, lib_off_dev, base_pos_dev, states_dev, pc, stride, W);
-        SQGR_HIP(hipGetLastError());
-        return SQGR_OK;
-    }
     int64_t n_pad = 0;
     SQGR_TRY(pcg_shuffle_rows(ctx, ws, n, n_libs, lib_off_dev, base_pos_dev, states_dev, pc, st, timer_name, &n_pad));
     {
@@ -1869,18 +1197,12 @@ int pcg_permutations_dev(sqgr_ctx* ctx, PcgWorkspace& ws, int64_t n, const uint6
         SQGR_HIP(hipMemcpy(ws.span.p, span_h, 8, hipMemcpyHostToDevice));
     }
     LaunchTimer t(ctx, "autocorr_pcg64_permutation", st);
-    if (pcg_lane_kernel()) {
-        const int64_t stride = ceil_div(pc, 64) * 64;
-        SQGR_TRY(ws.cols.ensure((size_t)n * stride));
-        k_pcg_shuffle<int32_t, true><<<(unsigned)ceil_div(pc, 64), 64, 0, st>>>(n, 1, ws.span.p, nullptr, states_dev, pc, stride, ws.cols.p);
-        k_columns_to_rows_i32<<<dim3((unsigned)ceil_div(n, 32), (unsigned)ceil_div(pc, 32)), 256, 0, st>>>(n, stride, ws.cols.p, pc, idx_dev);
-    } else {  // rows are the wanted output already: idx[q][i]
-        SQGR_TRY(ensure_pcg_jump(ws.jump));
-        const uint32_t wsz = pcg_window(n);
-        SQGR_TRY(pcg_allow_lds(k_pcg_shuffle_wave<int32_t, true>, (size_t)wsz * 4));
-        k_pcg_shuffle_wave<int32_t, true><<<pcg_grid(pc), 64, (size_t)wsz * 4, st>>>(n, n, 1, ws.span.p, nullptr, states_dev, ws.jump.p, pc,
-                                                                                     idx_dev, pcg_force_slow(), wsz);
-    }
+    SQGR_TRY(ensure_pcg_jump(ws.jump));
+    const uint32_t wsz = pcg_window(n);
+    SQGR_TRY(pcg_allow_lds(k_pcg_shuffle_wave<int32_t, true>, (size_t)wsz * 4));
+    // the kernel's rows are the wanted output already: idx[q][i]
+    k_pcg_shuffle_wave<int32_t, true><<<(unsigned)pc, 64, (size_t)wsz * 4, st>>>(n, n, 1, ws.span.p, nullptr, states_dev, ws.jump.p, pc, idx_dev,
+                                                                                 pcg_force_slow(), wsz);
     SQGR_HIP(hipGetLastError());
     return SQGR_OK;
 }

@@ -489,18 +489,16 @@ def g_identity_indices(n):
     return np.arange(n)
 
 
-@pytest.mark.parametrize("variant", ["wave", "wave-slow-path-only", "lane"])
+@pytest.mark.parametrize("variant", ["wave", "wave-slow-path-only"])
 def test_numpy_shuffle_kernel_variants_agree_with_numpy(L, ctx, variant, monkeypatch):
     """The wave-per-permutation shuffle (jump-ahead draws, parallel swaps, exact replay where a chunk has coinciding
-    draws / borderline candidates / a mask change / a library end), the same kernel forced onto its replay path, and
-    the one-thread-per-permutation kernel must all reproduce numpy bit for bit — sizes around the 64-draw chunk and
-    the 192-element fast-path limit, and libraries that end in the middle of a chunk."""
+    draws / borderline candidates / a mask change / a library end) and the same kernel forced onto its replay path
+    must both reproduce numpy bit for bit — sizes around the 64-draw chunk and the 192-element fast-path limit, and
+    libraries that end in the middle of a chunk."""
     from squidpy_amd._utils import pcg64_states
 
     if variant == "wave-slow-path-only":
         monkeypatch.setenv("SQGR_PCG_FORCE_SLOW", "1")
-    elif variant == "lane":
-        monkeypatch.setenv("SQGR_PCG_KERNEL", "lane")
     for n in (2, 3, 63, 64, 65, 128, 191, 192, 193, 257, 1000, 4097, 33000):
         P = 66
         got = L.pcg64_permutations(ctx, n, pcg64_states(n, P))
@@ -575,16 +573,13 @@ def test_numpy_shuffle_bucketed_replay_agrees_with_numpy(L, ctx, logs, monkeypat
         {"SQGR_PCG_QUEUE_CAP": "4"},                              # the replay's queue overflows at once: records stay with their lanes (spill path), a drain per chunk
         {"SQGR_PCG_QUEUE_CAP": "64"},
         {"SQGR_PCG_FORCE_SLOW": "1"},                             # the generator's one-by-one path on every trip (128 slots in order)
-        {"SQGR_PCG_APPLY": "tags", "SQGR_PCG_DRAWS": "64"},       # rounds 4-5's kernels stay selectable and correct
-        {"SQGR_PCG_APPLY": "tags"},                               # 128-draw generator + hashed-tag replay
-        {"SQGR_PCG_DRAWS": "64"},                                 # 64-draw generator + claims replay
     ],
     ids=lambda e: ",".join(f"{k[9:].lower()}={v}" for k, v in e.items()),
 )
 def test_numpy_shuffle_replay_variants_agree_with_numpy(L, ctx, env, monkeypatch):
     """Round 6's generator (128 draws per trip, one 64-record ring per range) and replay (exact claims, deferred queue, priority
-    drains): the paths a production run hardly takes — a full queue, the one-by-one acceptance — and the old kernels behind their
-    switches, against numpy's own shuffles: production geometry on 70 001 and 200 001 positions, 4096-position phases on 33 000."""
+    drains): the paths a production run hardly takes — a full queue, the one-by-one acceptance — against numpy's own shuffles:
+    production geometry on 70 001 and 200 001 positions, 4096-position phases on 33 000."""
     from squidpy_amd._utils import pcg64_states
 
     monkeypatch.setenv("SQGR_PCG_KERNEL", "bucket")

@@ -1,5 +1,5 @@
 """The re-ordering argument behind the device's bucketed replay of ``Generator.shuffle`` (csrc/sqgr_pcg.hip:
-k_pcg_draws_bucketed + k_pcg_apply_bucketed), checked against numpy itself on the CPU through its numpy restatement
+k_pcg_draws_bucketed2 + k_pcg_apply_claims), checked against numpy itself on the CPU through its numpy restatement
 ``oracle/pcg_bucket.py``: draws as numpy takes them, swaps applied phase by phase and RANGE BY RANGE with concurrent rounds."""
 
 import numpy as np

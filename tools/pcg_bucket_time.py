@@ -15,15 +15,12 @@ g = L.Graph(ctx, adj, with_data=False)
 st = pcg64_states(0, P)
 res = {}
 for kern in (sys.argv[2].split(",") if len(sys.argv) > 2 else ["bucket", "wave"]):
-    os.environ["SQGR_PCG_KERNEL"] = kern.split(":")[0].replace("bucket-tags", "bucket")
-    os.environ["SQGR_PCG_APPLY"] = "tags" if kern.startswith("bucket-tags") else "claims"   # replay kernel: rounds 4-5's hashed tags | exact claims
-    os.environ["SQGR_PCG_DRAWS"] = "64" if kern.startswith("bucket-tags") else "128"        # generator: 64 | 128 draws per trip
-    parts = kern.split(":")   # bucket[-tags][:logS[:tag slots]]
-    for var, idx in (("SQGR_PCG_BUCKET_LOGS", 1), ("SQGR_PCG_BUCKET_SLOTS", 2)):
-        if len(parts) > idx and parts[idx]:
-            os.environ[var] = parts[idx]
-        else:
-            os.environ.pop(var, None)
+    parts = kern.split(":")   # bucket[:logS] | wave
+    os.environ["SQGR_PCG_KERNEL"] = parts[0]
+    if len(parts) > 1 and parts[1]:
+        os.environ["SQGR_PCG_BUCKET_LOGS"] = parts[1]
+    else:
+        os.environ.pop("SQGR_PCG_BUCKET_LOGS", None)
     plan = L.NhoodPlan(ctx, g, labels, 30)
     plan.run_pcg64(st[:256])
     ctx.timer_enable(True); ctx.timer_reset()
