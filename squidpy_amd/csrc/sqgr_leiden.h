@@ -1,14 +1,13 @@
 // libsqgr: what sqgr_leiden.hip (one graph) and sqgr_leiden_multiplex.hip (two layers over the same vertices) share: the constants of
 // the contract, the hash and the priority of the independent set, the candidate order, the table insert, and the kernels that see one
 // CSR at a time (row sums, the input check, tot, the split sums of Q, renumbering and the coarse CSR).  Every kernel here is one
-// layer's; the two-layer code runs them once per layer.
+// layer's; the host driver that both run (sqgr_leiden_driver.h) launches them once per layer.
 #ifndef SQGR_LEIDEN_H
 #define SQGR_LEIDEN_H
 
 #include "sqgr_common.h"
 
 #include <algorithm>
-#include <cstddef>
 #include <vector>
 
 namespace sqgr {

@@ -27,15 +27,10 @@
 // k_best: a row of up to LD_CAP entries is one wave's, its neighbour communities in an LDS table of LD_SLOTS slots (open addressing,
 // 32-bit compare-and-swap on the key, 64-bit LDS add on the weight); longer rows (hubs, coarse levels) are one block's each, with a
 // table of twice the row's length in global memory.  Both paths form the same integers and pick by the same order.
-#include "sqgr_leiden.h"
-
-#include <rocprim/rocprim.hpp>
-
-#include <algorithm>
-#include <cmath>
-#include <cstddef>
-#include <numeric>
-#include <vector>
+//
+// This file holds k_best, k_apply, the sweep that launches them, Q, and the entry points; the kernels that see one CSR are in
+// sqgr_leiden.h, and the host driver, which the two-layer sqgr_leiden_multiplex.hip runs too, is in sqgr_leiden_driver.h.
+#include "sqgr_leiden_driver.h"
 
 namespace sqgr {
 namespace {
@@ -221,256 +216,52 @@ __global__ __launch_bounds__(LD_T) void k_apply(LevelView L, const int32_t* __re
     }
 }
 
-struct Leiden {
-    sqgr_ctx* ctx;
-    hipStream_t st;
-    unsigned grid;  // blocks of the grid-stride kernels
-    double gamma, two_m_d;
-    int64_t two_m;
-    int64_t n0, nnz0;
-    LevelBuf g0, ga, gb;
-    DevBuf<int32_t> comm, best_comm, want, rcomm, rsize, flags, newid, nr, pmin, ccomm, node_of, long_rows, tkeys;
-    DevBuf<int64_t> tot, dk, rtot, rext, vext, sw_out, mk_best, mtot_target;
-    DevBuf<double> mg_own;
-    DevBuf<unsigned long long> mclaimed, mfirst;
-    DevBuf<unsigned long long> tvals;
-    DevBuf<uint64_t> keys_in, keys_out, ukeys;
-    DevBuf<char> temp;
-    DevBuf<Acc> acc;
-    DevBuf<int64_t> n_unique;
-    int64_t n_long = 0;
-    int64_t stat_levels = 0, stat_sweeps = 0, stat_cap_hits = 0;
+struct OneLayer {
+    static constexpr const char* NAME = "sqgr_leiden";
+    static std::string where(int) { return NAME; }
 
-    unsigned blocks(int64_t items) const { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, LD_T), grid)); }
-    unsigned wave_blocks(int64_t rows) const { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(rows, LD_WAVES), grid)); }
-
-    int read_acc(Acc* h) {
-        SQGR_HIP(hipMemcpyAsync(h, acc.p, sizeof(Acc), hipMemcpyDeviceToHost, st));
-        SQGR_HIP(hipStreamSynchronize(st));
-        return SQGR_OK;
-    }
-
-    // k, erow and the long rows of a level whose CSR is in place
-    int prepare(LevelBuf& g) {
-        SQGR_HIP(hipMemsetAsync(&acc.p->two_m, 0, 3 * sizeof(unsigned long long), st));  // two_m[2] and n_long
-        {
-            LaunchTimer t(ctx, "leiden_rows");
-            k_rows<<<wave_blocks(g.n), LD_T, 0, st>>>(g.n, g.indptr.p, g.w.p, g.k.p, g.erow.p, long_rows.p, acc.p);
-            SQGR_HIP(hipGetLastError());
-        }
-        Acc h;
-        SQGR_TRY(read_acc(&h));
-        n_long = (int64_t)h.n_long;
-        if (n_long && !tkeys.p) {  // the global tables: two slots per stored entry of the largest level
-            SQGR_TRY(tkeys.alloc_pooled(2 * (size_t)(nnz0 + n0)));
-            SQGR_TRY(tvals.alloc_pooled(2 * (size_t)(nnz0 + n0)));
-        }
-        return SQGR_OK;
-    }
-
-    int rebuild_tot(const LevelBuf& g) {
-        SQGR_HIP(hipMemsetAsync(tot.p, 0, (size_t)g.n * 8, st));
-        LaunchTimer t(ctx, "leiden_tot");
-        k_tot<<<blocks(g.n), LD_T, 0, st>>>(g.n, comm.p, g.k.p, tot.p);
-        SQGR_HIP(hipGetLastError());
-        return SQGR_OK;
-    }
-
-    template <bool REFINE>
-    int sweep(const LevelBuf& g, uint32_t s) {
-        const LevelView L = g.view();
-        const MoveView M{mk_best.p, mg_own.p, mtot_target.p, mclaimed.p, mfirst.p};
+    template <bool REFINE, class D>
+    static int sweep(D& d, const Level<1>& g, uint32_t s) {
+        sqgr_ctx* const ctx = d.ctx;
+        hipStream_t const st = d.st;
+        const LevelView L = g.l[0].view();
+        const double gamma = d.gamma[0], two_m = (double)d.two_m[0];
+        const MoveView M{d.mk_best[0].p, d.mg_own.p, d.mtot_target[0].p, d.mclaimed[0].p, d.mfirst.p};
         if (!REFINE) {
-            SQGR_HIP(hipMemsetAsync(mclaimed.p, 0, (size_t)g.n * 8, st));
-            SQGR_HIP(hipMemsetAsync(mfirst.p, 0xff, (size_t)g.n * 8, st));
+            SQGR_HIP(hipMemsetAsync(d.mclaimed[0].p, 0, (size_t)g.n * 8, st));
+            SQGR_HIP(hipMemsetAsync(d.mfirst.p, 0xff, (size_t)g.n * 8, st));
         }
-        const RefineView R = REFINE ? RefineView{rcomm.p, rtot.p, rext.p, rsize.p, vext.p} : RefineView{nullptr, nullptr, nullptr, nullptr, nullptr};
+        const RefineView R = REFINE ? RefineView{d.rcomm.p, d.rtot[0].p, d.rext[0].p, d.rsize.p, d.vext[0].p}
+                                    : RefineView{nullptr, nullptr, nullptr, nullptr, nullptr};
         {
             LaunchTimer t(ctx, REFINE ? "leiden_refine_best" : "leiden_move_best");
-            k_best<false, REFINE><<<wave_blocks(g.n), LD_T, 0, st>>>(L, comm.p, tot.p, R, gamma, two_m_d, nullptr, 0, nullptr, nullptr, want.p, dk.p, M, s);
+            k_best<false, REFINE><<<d.wave_blocks(g.n), LD_T, 0, st>>>(L, d.comm.p, d.tot[0].p, R, gamma, two_m, nullptr, 0, nullptr, nullptr, d.want.p,
+                                                                      d.dk[0].p, M, s);
             SQGR_HIP(hipGetLastError());
         }
-        if (n_long) {
+        if (d.n_long) {
             LaunchTimer t(ctx, REFINE ? "leiden_refine_best_long" : "leiden_move_best_long");
-            k_best<true, REFINE><<<(unsigned)std::min<int64_t>(n_long, grid), LD_T, 0, st>>>(L, comm.p, tot.p, R, gamma, two_m_d, long_rows.p, n_long,
-                                                                                            tkeys.p, tvals.p, want.p, dk.p, M, s);
+            k_best<true, REFINE><<<(unsigned)std::min<int64_t>(d.n_long, d.grid), LD_T, 0, st>>>(L, d.comm.p, d.tot[0].p, R, gamma, two_m, d.long_rows.p,
+                                                                                                d.n_long, d.tkeys.p, d.tvals[0].p, d.want.p, d.dk[0].p, M, s);
             SQGR_HIP(hipGetLastError());
         }
         {
             LaunchTimer t(ctx, REFINE ? "leiden_refine_apply" : "leiden_move_apply");
             if (REFINE)
-                k_apply<true><<<wave_blocks(g.n), LD_T, 0, st>>>(L, want.p, dk.p, s, rcomm.p, rtot.p, rsize.p, rext.p, vext.p, acc.p, M, gamma, two_m_d);
+                k_apply<true><<<d.wave_blocks(g.n), LD_T, 0, st>>>(L, d.want.p, d.dk[0].p, s, d.rcomm.p, d.rtot[0].p, d.rsize.p, d.rext[0].p, d.vext[0].p,
+                                                                   d.acc.p, M, gamma, two_m);
             else
-                k_apply<false><<<wave_blocks(g.n), LD_T, 0, st>>>(L, want.p, dk.p, s, comm.p, tot.p, nullptr, nullptr, nullptr, acc.p, M, gamma, two_m_d);
+                k_apply<false><<<d.wave_blocks(g.n), LD_T, 0, st>>>(L, d.want.p, d.dk[0].p, s, d.comm.p, d.tot[0].p, nullptr, nullptr, nullptr, d.acc.p, M,
+                                                                    gamma, two_m);
             SQGR_HIP(hipGetLastError());
         }
         return SQGR_OK;
     }
 
-    int sumsq(const LevelBuf& g) {
-        LaunchTimer t(ctx, "leiden_sumsq");
-        k_sumsq<<<blocks(g.n), LD_T, 0, st>>>(g.n, tot.p, acc.p);
-        SQGR_HIP(hipGetLastError());
-        return SQGR_OK;
-    }
-
-    static unsigned __int128 join_sq(const Acc& h) { return ld_join_sq(h); }
-
-    int local_moving(const LevelBuf& g) {
-        SQGR_HIP(hipMemsetAsync(acc.p, 0, offsetof(Acc, two_m), st));  // moves, sum_in, sq
-        if (g.nnz) {
-            LaunchTimer t(ctx, "leiden_sum_in");
-            k_sum_in<<<blocks(g.nnz), LD_T, 0, st>>>(g.nnz, g.erow.p, g.indices.p, g.w.p, comm.p, acc.p);
-            SQGR_HIP(hipGetLastError());
-        }
-        SQGR_TRY(sumsq(g));
-        Acc h;
-        SQGR_TRY(read_acc(&h));
-        double best_q = ld_quality(h.sum_in, join_sq(h), gamma, two_m);
-        SQGR_HIP(hipMemcpyAsync(best_comm.p, comm.p, (size_t)g.n * 4, hipMemcpyDeviceToDevice, st));
-        bool converged = false;
-        for (int s = 0; s < LD_SWEEP_CAP; ++s) {
-            SQGR_HIP(hipMemsetAsync(&acc.p->moves, 0, 8, st));
-            SQGR_HIP(hipMemsetAsync(&acc.p->sq, 0, 24, st));
-            SQGR_TRY(sweep<false>(g, (uint32_t)s));
-            SQGR_TRY(sumsq(g));
-            SQGR_TRY(read_acc(&h));
-            ++stat_sweeps;
-            if (!h.moves) {
-                converged = true;
-                break;
-            }
-            const double q = ld_quality(h.sum_in, join_sq(h), gamma, two_m);
-            if (q > best_q) {
-                best_q = q;
-                SQGR_HIP(hipMemcpyAsync(best_comm.p, comm.p, (size_t)g.n * 4, hipMemcpyDeviceToDevice, st));
-            }
-        }
-        if (!converged) {  // the cap: the assignment of largest Q seen
-            ++stat_cap_hits;
-            SQGR_HIP(hipMemcpyAsync(comm.p, best_comm.p, (size_t)g.n * 4, hipMemcpyDeviceToDevice, st));
-            SQGR_TRY(rebuild_tot(g));
-        }
-        return SQGR_OK;
-    }
-
-    int count_distinct(int64_t n, const int32_t* ids, int64_t* out) {
-        SQGR_HIP(hipMemsetAsync(flags.p, 0, (size_t)n * 4, st));
-        SQGR_HIP(hipMemsetAsync(&acc.p->count, 0, 8, st));
-        k_flag<<<blocks(n), LD_T, 0, st>>>(n, ids, flags.p);
-        SQGR_HIP(hipGetLastError());
-        k_count_flags<<<blocks(n), LD_T, 0, st>>>(n, flags.p, acc.p);
-        SQGR_HIP(hipGetLastError());
-        Acc h;
-        SQGR_TRY(read_acc(&h));
-        *out = (int64_t)h.count;
-        return SQGR_OK;
-    }
-
-    int refine(const LevelBuf& g) {
-        {
-            LaunchTimer t(ctx, "leiden_refine_init");
-            k_refine_init<<<wave_blocks(g.n), LD_T, 0, st>>>(g.view(), comm.p, rcomm.p, rtot.p, rext.p, rsize.p, vext.p);
-            SQGR_HIP(hipGetLastError());
-        }
-        for (int s = 0; s < LD_SWEEP_CAP; ++s) {
-            SQGR_HIP(hipMemsetAsync(&acc.p->moves, 0, 8, st));
-            SQGR_TRY(sweep<true>(g, (uint32_t)s));
-            Acc h;
-            SQGR_TRY(read_acc(&h));
-            ++stat_sweeps;
-            if (!h.moves) break;
-        }
-        return SQGR_OK;
-    }
-
-    int ensure_temp(size_t bytes) { return temp.ensure(std::max<size_t>(bytes, 16)); }
-
-    // the refined communities of level g become the nodes of `out`; *n_coarse == g.n: nothing merged and `out` is not built
-    int aggregate(const LevelBuf& g, LevelBuf& out, int64_t* n_coarse) {
-        const int64_t n = g.n, nnz = g.nnz;
-        SQGR_HIP(hipMemsetAsync(flags.p, 0, (size_t)n * 4, st));
-        k_flag<<<blocks(n), LD_T, 0, st>>>(n, rcomm.p, flags.p);
-        SQGR_HIP(hipGetLastError());
-        size_t tb = 0;
-        SQGR_HIP(rocprim::exclusive_scan(nullptr, tb, flags.p, newid.p, 0, (size_t)n, rocprim::plus<int32_t>(), st));
-        SQGR_TRY(ensure_temp(tb));
-        {
-            LaunchTimer t(ctx, "leiden_renumber");
-            SQGR_HIP(rocprim::exclusive_scan(temp.p, tb, flags.p, newid.p, 0, (size_t)n, rocprim::plus<int32_t>(), st));
-        }
-        int32_t last[2];
-        SQGR_HIP(hipMemcpyAsync(&last[0], newid.p + (n - 1), 4, hipMemcpyDeviceToHost, st));
-        SQGR_HIP(hipMemcpyAsync(&last[1], flags.p + (n - 1), 4, hipMemcpyDeviceToHost, st));
-        SQGR_HIP(hipStreamSynchronize(st));
-        const int64_t nc = (int64_t)last[0] + last[1];
-        *n_coarse = nc;
-        if (nc == n) return SQGR_OK;
-        SQGR_HIP(hipMemsetAsync(pmin.p, 0x7f, (size_t)n * 4, st));
-        k_relabel<<<blocks(n), LD_T, 0, st>>>(n, rcomm.p, newid.p, comm.p, nr.p, pmin.p);
-        SQGR_HIP(hipGetLastError());
-        k_coarse_comm<<<blocks(n), LD_T, 0, st>>>(n, nr.p, comm.p, pmin.p, ccomm.p);
-        SQGR_HIP(hipGetLastError());
-        k_compose<<<blocks(n0), LD_T, 0, st>>>(n0, nr.p, node_of.p);
-        SQGR_HIP(hipGetLastError());
-        int64_t m = 0;
-        if (nnz) {
-            k_edge_keys<<<blocks(nnz), LD_T, 0, st>>>(nnz, g.erow.p, g.indices.p, nr.p, keys_in.p);
-            SQGR_HIP(hipGetLastError());
-            SQGR_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys_in.p, keys_out.p, g.w.p, sw_out.p, (size_t)nnz, 0, 64, st));
-            SQGR_TRY(ensure_temp(tb));
-            {
-                LaunchTimer t(ctx, "leiden_sort");
-                SQGR_HIP(rocprim::radix_sort_pairs(temp.p, tb, keys_in.p, keys_out.p, g.w.p, sw_out.p, (size_t)nnz, 0, 64, st));
-            }
-            SQGR_HIP(rocprim::reduce_by_key(nullptr, tb, keys_out.p, sw_out.p, (size_t)nnz, ukeys.p, out.w.p, n_unique.p, rocprim::plus<int64_t>(),
-                                            rocprim::equal_to<uint64_t>(), st));
-            SQGR_TRY(ensure_temp(tb));
-            {
-                LaunchTimer t(ctx, "leiden_reduce");
-                SQGR_HIP(rocprim::reduce_by_key(temp.p, tb, keys_out.p, sw_out.p, (size_t)nnz, ukeys.p, out.w.p, n_unique.p,
-                                                rocprim::plus<int64_t>(), rocprim::equal_to<uint64_t>(), st));
-            }
-            SQGR_HIP(hipMemcpyAsync(&m, n_unique.p, 8, hipMemcpyDeviceToHost, st));
-            SQGR_HIP(hipStreamSynchronize(st));
-            if (m < 0 || m > nnz) {
-                set_error("sqgr_leiden: reduce_by_key returned %lld groups of %lld entries", (long long)m, (long long)nnz);
-                return SQGR_ERR_HIP;
-            }
-            k_coarse_cols<<<blocks(m), LD_T, 0, st>>>(m, ukeys.p, out.indices.p);
-            SQGR_HIP(hipGetLastError());
-        }
-        k_coarse_indptr<<<blocks(nc + 1), LD_T, 0, st>>>(nc, m, ukeys.p, out.indptr.p);
-        SQGR_HIP(hipGetLastError());
-        out.n = nc;
-        out.nnz = m;
-        return SQGR_OK;
-    }
-
-    // one iteration from comm (level 0 ids); leaves node_of
-    int iterate() {
-        {
-            k_iota<<<blocks(n0), LD_T, 0, st>>>(n0, node_of.p);
-            SQGR_HIP(hipGetLastError());
-        }
-        LevelBuf* cur = &g0;
-        for (;;) {
-            ++stat_levels;
-            SQGR_TRY(prepare(*cur));
-            SQGR_TRY(rebuild_tot(*cur));
-            SQGR_TRY(local_moving(*cur));
-            int64_t kp = 0;
-            SQGR_TRY(count_distinct(cur->n, comm.p, &kp));
-            if (kp == cur->n) break;
-            SQGR_TRY(refine(*cur));
-            LevelBuf* next = cur == &ga ? &gb : &ga;
-            int64_t nc = 0;
-            SQGR_TRY(aggregate(*cur, *next, &nc));
-            if (nc == cur->n) break;
-            SQGR_HIP(hipMemcpyAsync(comm.p, ccomm.p, (size_t)nc * 4, hipMemcpyDeviceToDevice, st));
-            cur = next;
-        }
-        return SQGR_OK;
+    // the single-layer expression itself, not the two-layer mix of it: one more multiplication could turn q > best_q into a tie
+    template <class D>
+    static double quality(const D& d, const Acc* h) {
+        return ld_quality(h[0].sum_in, ld_join_sq(h[0]), d.gamma[0], d.two_m[0]);
     }
 };
 
@@ -486,130 +277,11 @@ int sqgr_leiden_info(int64_t* out_info) {
     out_info[2] = LD_ITER_CAP;
     out_info[3] = LD_CAP;
     out_info[4] = LD_SLOTS;
-    out_info[5] = 8;  // entries of out_stats
+    out_info[5] = ld_n_stats(1);  // entries of out_stats
     return SQGR_OK;
 }
 
 int sqgr_leiden(sqgr_ctx* ctx, int64_t n, const int64_t* indptr, const int32_t* indices, const int32_t* weights, double resolution,
                 int32_t n_iterations, int32_t* out_labels, int64_t* out_stats) {
-    SQGR_REQUIRE(ctx && indptr && out_labels && out_stats, "null argument");
-    SQGR_REQUIRE(n >= 1, "sqgr_leiden: n=%lld", (long long)n);
-    SQGR_REQUIRE(std::isfinite(resolution) && resolution > 0, "sqgr_leiden: resolution=%g must be finite and positive", resolution);
-    SQGR_REQUIRE(n_iterations != 0, "sqgr_leiden: n_iterations=0 (a positive count, or negative for: until an iteration changes nothing)");
-    if (n >= ((int64_t)1 << 31) - 1) {
-        set_error("sqgr_leiden: n=%lld, vertex ids are 32-bit", (long long)n);
-        return SQGR_ERR_UNSUPPORTED;
-    }
-    SQGR_REQUIRE(indptr[0] == 0, "sqgr_leiden: indptr[0]=%lld", (long long)indptr[0]);
-    for (int64_t i = 0; i < n; ++i) SQGR_REQUIRE(indptr[i + 1] >= indptr[i], "sqgr_leiden: indptr decreases at row %lld", (long long)i);
-    const int64_t nnz = indptr[n];
-    SQGR_REQUIRE(nnz == 0 || (indices && weights), "null argument");
-    if (nnz >= ((int64_t)1 << 36)) {
-        set_error("sqgr_leiden: nnz=%lld", (long long)nnz);
-        return SQGR_ERR_UNSUPPORTED;
-    }
-    for (int i = 0; i < 8; ++i) out_stats[i] = 0;
-    if (nnz == 0) {  // 2m = 0: every vertex is its own community
-        for (int64_t i = 0; i < n; ++i) out_labels[i] = (int32_t)i;
-        out_stats[0] = n;
-        out_stats[7] = 1;
-        return SQGR_OK;
-    }
-    SQGR_HIP(hipSetDevice(ctx->device));
-    Leiden S;
-    S.ctx = ctx;
-    S.st = ctx->stream;
-    S.grid = 8u * (unsigned)std::max(ctx->cu_count, 1);
-    S.gamma = resolution;
-    S.n0 = n;
-    S.nnz0 = nnz;
-    hipStream_t st = S.st;
-    const size_t ncap = (size_t)n, ecap = (size_t)nnz + (size_t)n;  // a coarse level has fewer nodes and at most one self loop per node more
-    SQGR_TRY(S.g0.alloc(n, nnz));
-    SQGR_TRY(S.ga.alloc(n, (int64_t)ecap));
-    SQGR_TRY(S.gb.alloc(n, (int64_t)ecap));
-    for (DevBuf<int32_t>* b : {&S.comm, &S.best_comm, &S.want, &S.rcomm, &S.rsize, &S.flags, &S.newid, &S.nr, &S.pmin, &S.ccomm, &S.node_of, &S.long_rows})
-        SQGR_TRY(b->alloc(ncap));
-    for (DevBuf<int64_t>* b : {&S.tot, &S.dk, &S.rtot, &S.rext, &S.vext, &S.mk_best, &S.mtot_target}) SQGR_TRY(b->alloc(ncap));
-    SQGR_TRY(S.mg_own.alloc(ncap));
-    SQGR_TRY(S.mclaimed.alloc(ncap));
-    SQGR_TRY(S.mfirst.alloc(ncap));
-    SQGR_TRY(S.sw_out.alloc(ecap));
-    SQGR_TRY(S.keys_in.alloc(ecap));
-    SQGR_TRY(S.keys_out.alloc(ecap));
-    SQGR_TRY(S.ukeys.alloc(ecap));
-    SQGR_TRY(S.acc.alloc(1));
-    SQGR_TRY(S.n_unique.alloc(1));
-    SQGR_HIP(hipMemsetAsync(S.acc.p, 0, sizeof(Acc), st));
-
-    // upload and check
-    DevBuf<int32_t> w32;
-    DevBuf<int> flags;
-    SQGR_TRY(w32.alloc((size_t)nnz));
-    SQGR_TRY(flags.alloc(5));
-    SQGR_HIP(hipMemsetAsync(flags.p, 0, 5 * sizeof(int), st));
-    SQGR_HIP(hipMemcpyAsync(S.g0.indptr.p, indptr, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
-    SQGR_HIP(hipMemcpyAsync(S.g0.indices.p, indices, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
-    SQGR_HIP(hipMemcpyAsync(w32.p, weights, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
-    S.g0.n = n;
-    S.g0.nnz = nnz;
-    k_widen<<<S.blocks(nnz), LD_T, 0, st>>>(w32.p, nnz, S.g0.w.p);
-    SQGR_HIP(hipGetLastError());
-    SQGR_TRY(S.prepare(S.g0));  // erow (indptr alone decides it), k, 2m
-    {
-        LaunchTimer t(ctx, "leiden_check");
-        k_check<<<S.blocks(nnz), LD_T, 0, st>>>(n, S.g0.indptr.p, S.g0.indices.p, w32.p, S.g0.erow.p, nnz, flags.p);
-        SQGR_HIP(hipGetLastError());
-    }
-    int hf[5] = {1, 1, 1, 1, 1};
-    Acc hacc;
-    SQGR_HIP(hipMemcpyAsync(hf, flags.p, sizeof(hf), hipMemcpyDeviceToHost, st));
-    SQGR_TRY(S.read_acc(&hacc));
-    SQGR_REQUIRE(!hf[4], "sqgr_leiden: a column index is outside [0, n)");
-    SQGR_REQUIRE(!hf[3], "sqgr_leiden: a weight is smaller than 1");
-    SQGR_REQUIRE(!hf[1], "sqgr_leiden: a row of the graph is not sorted or repeats an entry");
-    SQGR_REQUIRE(!hf[2], "sqgr_leiden: the graph has a self loop");
-    SQGR_REQUIRE(!hf[0], "sqgr_leiden: the graph is not symmetric (an entry without a mirror entry of equal weight)");
-    const unsigned __int128 two_m128 = (unsigned __int128)hacc.two_m[0] + ((unsigned __int128)hacc.two_m[1] << 32);
-    if (two_m128 >= ((unsigned __int128)1 << 62)) {
-        set_error("sqgr_leiden: the sum of all weights reaches 2^62");
-        return SQGR_ERR_UNSUPPORTED;
-    }
-    S.two_m = (int64_t)two_m128;
-    S.two_m_d = (double)S.two_m;
-
-    std::vector<int32_t> ids((size_t)n), labels((size_t)n), prev((size_t)n);
-    std::iota(prev.begin(), prev.end(), 0);  // the start: every vertex alone, which is canonical
-    const int max_it = n_iterations < 0 ? LD_ITER_CAP : n_iterations;
-    int64_t K = n, iterations = 0, settled = 0;
-    for (int it = 0; it < max_it; ++it) {
-        SQGR_HIP(hipMemcpyAsync(S.comm.p, prev.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-        SQGR_TRY(S.iterate());
-        SQGR_HIP(hipMemcpyAsync(ids.data(), S.node_of.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        SQGR_HIP(hipStreamSynchronize(st));
-        const int64_t k_new = canonical_labels(ids, n, labels.data());
-        ++iterations;
-        if (labels == prev) {
-            settled = 1;
-            break;
-        }
-        prev.swap(labels);
-        K = k_new;
-    }
-    // sum_c in_c of the result on the input graph
-    SQGR_HIP(hipMemcpyAsync(S.comm.p, prev.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-    SQGR_HIP(hipMemsetAsync(&S.acc.p->sum_in, 0, 8, st));
-    k_sum_in<<<S.blocks(nnz), LD_T, 0, st>>>(nnz, S.g0.erow.p, S.g0.indices.p, S.g0.w.p, S.comm.p, S.acc.p);
-    SQGR_HIP(hipGetLastError());
-    SQGR_TRY(S.read_acc(&hacc));
-    std::copy(prev.begin(), prev.end(), out_labels);
-    out_stats[0] = K;
-    out_stats[1] = iterations;
-    out_stats[2] = S.stat_levels;
-    out_stats[3] = S.stat_sweeps;
-    out_stats[4] = hacc.sum_in;
-    out_stats[5] = S.two_m;
-    out_stats[6] = S.stat_cap_hits;
-    out_stats[7] = settled;
-    return SQGR_OK;
+    return leiden_run<1, OneLayer>(ctx, n, &indptr, &indices, &weights, &resolution, 1.0, n_iterations, out_labels, out_stats);
 }

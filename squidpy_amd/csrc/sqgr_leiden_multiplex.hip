@@ -17,18 +17,15 @@
 //   aggregation   one coarse CSR per layer over the same refined-community numbering; a self loop carries in^l_c.
 // A row takes the on-chip path when its stored entries in layer 0 plus those in layer 1 are <= LD_CAP, else the global-memory path
 // with a table of twice that sum at 2 * (indptr0[v] + indptr1[v]).  Both paths form the same integers and pick by the same order.
-#include "sqgr_leiden.h"
-
-#include <rocprim/rocprim.hpp>
-
-#include <cmath>
-#include <numeric>
+//
+// This file holds what sees both layers at once: k_best2, k_apply2, k_long_rows2, the sweep that launches them, the mixed Q, and
+// the entry points.  The per-layer kernels are in sqgr_leiden.h; the host driver is sqgr_leiden.hip's, in sqgr_leiden_driver.h.
+#include "sqgr_leiden_driver.h"
 
 namespace sqgr {
 namespace {
 
 constexpr int MX_LAYERS = 2;
-constexpr int MX_STATS = 10;
 
 struct MxParams {
     double gamma[MX_LAYERS];
@@ -288,290 +285,70 @@ __global__ __launch_bounds__(LD_T) void k_long_rows2(int64_t n, const int64_t* _
         if ((indptr0[v + 1] - indptr0[v]) + (indptr1[v + 1] - indptr1[v]) > LD_CAP) long_rows[atomicAdd(&acc->n_long, 1ull)] = (int32_t)v;
 }
 
-struct MxLevelBuf {
-    LevelBuf l[MX_LAYERS];
-    int64_t n = 0;
-    MxLevel view() const { return MxLevel{{l[0].view(), l[1].view()}}; }
-};
+struct TwoLayers {
+    static constexpr const char* NAME = "sqgr_leiden_multiplex";
+    static std::string where(int l) { return std::string(NAME) + ": layer " + std::to_string(l); }
 
-struct Multiplex {
-    sqgr_ctx* ctx;
-    hipStream_t st;
-    unsigned grid;  // blocks of the grid-stride kernels
-    MxParams P;
-    int64_t two_m[MX_LAYERS];
-    int64_t n0, ecap[MX_LAYERS];
-    MxLevelBuf g0, ga, gb;
-    DevBuf<int32_t> comm, best_comm, want, rcomm, rsize, flags, newid, nr, pmin, ccomm, node_of, long_rows, tkeys;
-    DevBuf<int64_t> tot[MX_LAYERS], dk[MX_LAYERS], rtot[MX_LAYERS], rext[MX_LAYERS], vext[MX_LAYERS], mk_best[MX_LAYERS], mtot_target[MX_LAYERS];
-    DevBuf<int64_t> sw_out;
-    DevBuf<double> mg_own;
-    DevBuf<unsigned long long> mclaimed[MX_LAYERS], mfirst, tvals[MX_LAYERS];
-    DevBuf<uint64_t> keys_in, keys_out, ukeys;
-    DevBuf<char> temp;
-    DevBuf<Acc> acc;  // one per layer; moves, n_long and count live in acc[0]
-    DevBuf<int64_t> n_unique;
-    int64_t n_long = 0;
-    int64_t stat_levels = 0, stat_sweeps = 0, stat_cap_hits = 0;
-
-    unsigned blocks(int64_t items) const { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, LD_T), grid)); }
-    unsigned wave_blocks(int64_t rows) const { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(rows, LD_WAVES), grid)); }
-
-    int read_acc(Acc* h) {  // Acc[MX_LAYERS]
-        SQGR_HIP(hipMemcpyAsync(h, acc.p, MX_LAYERS * sizeof(Acc), hipMemcpyDeviceToHost, st));
-        SQGR_HIP(hipStreamSynchronize(st));
-        return SQGR_OK;
+    template <class D>
+    static MxParams params(const D& d) {
+        return MxParams{{d.gamma[0], d.gamma[1]}, {(double)d.two_m[0], (double)d.two_m[1]}, d.ratio};
     }
 
-    // k, erow and 2m per layer, and the long rows, of a level whose CSRs are in place
-    int prepare(MxLevelBuf& g, Acc* h) {
-        for (int l = 0; l < MX_LAYERS; ++l) {
-            SQGR_HIP(hipMemsetAsync(&acc.p[l].two_m, 0, 3 * sizeof(unsigned long long), st));  // two_m[2] and n_long
-            LaunchTimer t(ctx, "mleiden_rows");
-            k_rows<<<wave_blocks(g.n), LD_T, 0, st>>>(g.n, g.l[l].indptr.p, g.l[l].w.p, g.l[l].k.p, g.l[l].erow.p, nullptr, &acc.p[l]);
-            SQGR_HIP(hipGetLastError());
-        }
-        k_long_rows2<<<blocks(g.n), LD_T, 0, st>>>(g.n, g.l[0].indptr.p, g.l[1].indptr.p, long_rows.p, acc.p);
+    template <class D>
+    static int long_rows(D& d, const Level<MX_LAYERS>& g) {
+        k_long_rows2<<<d.blocks(g.n), LD_T, 0, d.st>>>(g.n, g.l[0].indptr.p, g.l[1].indptr.p, d.long_rows.p, d.acc.p);
         SQGR_HIP(hipGetLastError());
-        SQGR_TRY(read_acc(h));
-        n_long = (int64_t)h[0].n_long;
-        if (n_long && !tkeys.p) {  // the global tables: two slots per stored entry of both layers of the largest level
-            const size_t slots = 2 * (size_t)(ecap[0] + ecap[1]);
-            SQGR_TRY(tkeys.alloc_pooled(slots));
-            SQGR_TRY(tvals[0].alloc_pooled(slots));
-            SQGR_TRY(tvals[1].alloc_pooled(slots));
-        }
         return SQGR_OK;
     }
 
-    int rebuild_tot(const MxLevelBuf& g) {
-        for (int l = 0; l < MX_LAYERS; ++l) {
-            SQGR_HIP(hipMemsetAsync(tot[l].p, 0, (size_t)g.n * 8, st));
-            LaunchTimer t(ctx, "mleiden_tot");
-            k_tot<<<blocks(g.n), LD_T, 0, st>>>(g.n, comm.p, g.l[l].k.p, tot[l].p);
-            SQGR_HIP(hipGetLastError());
-        }
-        return SQGR_OK;
-    }
-
-    template <bool REFINE>
-    int sweep(const MxLevelBuf& g, uint32_t s) {
-        const MxLevel G = g.view();
-        const MxMove M{{mk_best[0].p, mk_best[1].p}, mg_own.p, {mtot_target[0].p, mtot_target[1].p}, {mclaimed[0].p, mclaimed[1].p}, mfirst.p};
+    template <bool REFINE, class D>
+    static int sweep(D& d, const Level<MX_LAYERS>& g, uint32_t s) {
+        sqgr_ctx* const ctx = d.ctx;
+        hipStream_t const st = d.st;
+        const MxLevel G{{g.l[0].view(), g.l[1].view()}};
+        const MxParams P = params(d);
+        const MxMove M{{d.mk_best[0].p, d.mk_best[1].p}, d.mg_own.p, {d.mtot_target[0].p, d.mtot_target[1].p}, {d.mclaimed[0].p, d.mclaimed[1].p},
+                       d.mfirst.p};
         if (!REFINE) {
-            SQGR_HIP(hipMemsetAsync(mclaimed[0].p, 0, (size_t)g.n * 8, st));
-            SQGR_HIP(hipMemsetAsync(mclaimed[1].p, 0, (size_t)g.n * 8, st));
-            SQGR_HIP(hipMemsetAsync(mfirst.p, 0xff, (size_t)g.n * 8, st));
+            SQGR_HIP(hipMemsetAsync(d.mclaimed[0].p, 0, (size_t)g.n * 8, st));
+            SQGR_HIP(hipMemsetAsync(d.mclaimed[1].p, 0, (size_t)g.n * 8, st));
+            SQGR_HIP(hipMemsetAsync(d.mfirst.p, 0xff, (size_t)g.n * 8, st));
         }
-        const MxRefine R = REFINE ? MxRefine{rcomm.p, rsize.p, {rtot[0].p, rtot[1].p}, {rext[0].p, rext[1].p}, {vext[0].p, vext[1].p}}
+        const MxRefine R = REFINE ? MxRefine{d.rcomm.p, d.rsize.p, {d.rtot[0].p, d.rtot[1].p}, {d.rext[0].p, d.rext[1].p}, {d.vext[0].p, d.vext[1].p}}
                                   : MxRefine{nullptr, nullptr, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
         {
             LaunchTimer t(ctx, REFINE ? "mleiden_refine_best" : "mleiden_move_best");
-            k_best2<false, REFINE><<<wave_blocks(g.n), LD_T, 0, st>>>(G, comm.p, tot[0].p, tot[1].p, R, P, nullptr, 0, nullptr, nullptr, nullptr, want.p,
-                                                                      dk[0].p, dk[1].p, M, s);
+            k_best2<false, REFINE><<<d.wave_blocks(g.n), LD_T, 0, st>>>(G, d.comm.p, d.tot[0].p, d.tot[1].p, R, P, nullptr, 0, nullptr, nullptr, nullptr,
+                                                                       d.want.p, d.dk[0].p, d.dk[1].p, M, s);
             SQGR_HIP(hipGetLastError());
         }
-        if (n_long) {
+        if (d.n_long) {
             LaunchTimer t(ctx, REFINE ? "mleiden_refine_best_long" : "mleiden_move_best_long");
-            k_best2<true, REFINE><<<(unsigned)std::min<int64_t>(n_long, grid), LD_T, 0, st>>>(G, comm.p, tot[0].p, tot[1].p, R, P, long_rows.p, n_long,
-                                                                                             tkeys.p, tvals[0].p, tvals[1].p, want.p, dk[0].p, dk[1].p, M, s);
+            k_best2<true, REFINE><<<(unsigned)std::min<int64_t>(d.n_long, d.grid), LD_T, 0, st>>>(G, d.comm.p, d.tot[0].p, d.tot[1].p, R, P, d.long_rows.p,
+                                                                                                 d.n_long, d.tkeys.p, d.tvals[0].p, d.tvals[1].p, d.want.p,
+                                                                                                 d.dk[0].p, d.dk[1].p, M, s);
             SQGR_HIP(hipGetLastError());
         }
         {
             LaunchTimer t(ctx, REFINE ? "mleiden_refine_apply" : "mleiden_move_apply");
             if (REFINE)
-                k_apply2<true><<<wave_blocks(g.n), LD_T, 0, st>>>(G, want.p, dk[0].p, dk[1].p, s, rcomm.p, rtot[0].p, rtot[1].p, rsize.p, rext[0].p,
-                                                                  rext[1].p, vext[0].p, vext[1].p, acc.p, M, P);
+                k_apply2<true><<<d.wave_blocks(g.n), LD_T, 0, st>>>(G, d.want.p, d.dk[0].p, d.dk[1].p, s, d.rcomm.p, d.rtot[0].p, d.rtot[1].p, d.rsize.p,
+                                                                    d.rext[0].p, d.rext[1].p, d.vext[0].p, d.vext[1].p, d.acc.p, M, P);
             else
-                k_apply2<false><<<wave_blocks(g.n), LD_T, 0, st>>>(G, want.p, dk[0].p, dk[1].p, s, comm.p, tot[0].p, tot[1].p, nullptr, nullptr, nullptr,
-                                                                   nullptr, nullptr, acc.p, M, P);
-            SQGR_HIP(hipGetLastError());
-        }
-        return SQGR_OK;
-    }
-
-    int sumsq(const MxLevelBuf& g) {
-        for (int l = 0; l < MX_LAYERS; ++l) {
-            LaunchTimer t(ctx, "mleiden_sumsq");
-            k_sumsq<<<blocks(g.n), LD_T, 0, st>>>(g.n, tot[l].p, &acc.p[l]);
+                k_apply2<false><<<d.wave_blocks(g.n), LD_T, 0, st>>>(G, d.want.p, d.dk[0].p, d.dk[1].p, s, d.comm.p, d.tot[0].p, d.tot[1].p, nullptr,
+                                                                     nullptr, nullptr, nullptr, nullptr, d.acc.p, M, P);
             SQGR_HIP(hipGetLastError());
         }
         return SQGR_OK;
     }
 
     // Q = (double)two_m_0 * q_0 + layer_ratio * ((double)two_m_1 * q_1), q_l the single-layer expression, 0 for a layer without weight
-    double quality(const Acc* h) const {
+    template <class D>
+    static double quality(const D& d, const Acc* h) {
         double part[MX_LAYERS];
         for (int l = 0; l < MX_LAYERS; ++l)
-            part[l] = two_m[l] ? (double)two_m[l] * ld_quality(h[l].sum_in, ld_join_sq(h[l]), P.gamma[l], two_m[l]) : 0.0;
-        return mx_mix(P, part[0], part[1]);
-    }
-
-    int local_moving(const MxLevelBuf& g) {
-        Acc h[MX_LAYERS];
-        for (int l = 0; l < MX_LAYERS; ++l) {
-            SQGR_HIP(hipMemsetAsync(&acc.p[l], 0, offsetof(Acc, two_m), st));  // moves, sum_in, sq
-            if (g.l[l].nnz) {
-                LaunchTimer t(ctx, "mleiden_sum_in");
-                k_sum_in<<<blocks(g.l[l].nnz), LD_T, 0, st>>>(g.l[l].nnz, g.l[l].erow.p, g.l[l].indices.p, g.l[l].w.p, comm.p, &acc.p[l]);
-                SQGR_HIP(hipGetLastError());
-            }
-        }
-        SQGR_TRY(sumsq(g));
-        SQGR_TRY(read_acc(h));
-        double best_q = quality(h);
-        SQGR_HIP(hipMemcpyAsync(best_comm.p, comm.p, (size_t)g.n * 4, hipMemcpyDeviceToDevice, st));
-        bool converged = false;
-        for (int s = 0; s < LD_SWEEP_CAP; ++s) {
-            SQGR_HIP(hipMemsetAsync(&acc.p[0].moves, 0, 8, st));
-            for (int l = 0; l < MX_LAYERS; ++l) SQGR_HIP(hipMemsetAsync(&acc.p[l].sq, 0, 24, st));
-            SQGR_TRY(sweep<false>(g, (uint32_t)s));
-            SQGR_TRY(sumsq(g));
-            SQGR_TRY(read_acc(h));
-            ++stat_sweeps;
-            if (!h[0].moves) {
-                converged = true;
-                break;
-            }
-            const double q = quality(h);
-            if (q > best_q) {
-                best_q = q;
-                SQGR_HIP(hipMemcpyAsync(best_comm.p, comm.p, (size_t)g.n * 4, hipMemcpyDeviceToDevice, st));
-            }
-        }
-        if (!converged) {  // the cap: the assignment of largest Q seen
-            ++stat_cap_hits;
-            SQGR_HIP(hipMemcpyAsync(comm.p, best_comm.p, (size_t)g.n * 4, hipMemcpyDeviceToDevice, st));
-            SQGR_TRY(rebuild_tot(g));
-        }
-        return SQGR_OK;
-    }
-
-    int count_distinct(int64_t n, const int32_t* ids, int64_t* out) {
-        SQGR_HIP(hipMemsetAsync(flags.p, 0, (size_t)n * 4, st));
-        SQGR_HIP(hipMemsetAsync(&acc.p[0].count, 0, 8, st));
-        k_flag<<<blocks(n), LD_T, 0, st>>>(n, ids, flags.p);
-        SQGR_HIP(hipGetLastError());
-        k_count_flags<<<blocks(n), LD_T, 0, st>>>(n, flags.p, acc.p);
-        SQGR_HIP(hipGetLastError());
-        Acc h[MX_LAYERS];
-        SQGR_TRY(read_acc(h));
-        *out = (int64_t)h[0].count;
-        return SQGR_OK;
-    }
-
-    int refine(const MxLevelBuf& g) {
-        for (int l = 0; l < MX_LAYERS; ++l) {  // rcomm and rsize are written by both launches, with the same values
-            LaunchTimer t(ctx, "mleiden_refine_init");
-            k_refine_init<<<wave_blocks(g.n), LD_T, 0, st>>>(g.l[l].view(), comm.p, rcomm.p, rtot[l].p, rext[l].p, rsize.p, vext[l].p);
-            SQGR_HIP(hipGetLastError());
-        }
-        for (int s = 0; s < LD_SWEEP_CAP; ++s) {
-            SQGR_HIP(hipMemsetAsync(&acc.p[0].moves, 0, 8, st));
-            SQGR_TRY(sweep<true>(g, (uint32_t)s));
-            Acc h[MX_LAYERS];
-            SQGR_TRY(read_acc(h));
-            ++stat_sweeps;
-            if (!h[0].moves) break;
-        }
-        return SQGR_OK;
-    }
-
-    int ensure_temp(size_t bytes) { return temp.ensure(std::max<size_t>(bytes, 16)); }
-
-    // one layer's coarse CSR over the numbering nr: parallel entries summed, the inner weight on the self loop
-    int coarse_layer(const LevelBuf& g, LevelBuf& out, int64_t nc) {
-        const int64_t nnz = g.nnz;
-        size_t tb = 0;
-        int64_t m = 0;
-        if (nnz) {
-            k_edge_keys<<<blocks(nnz), LD_T, 0, st>>>(nnz, g.erow.p, g.indices.p, nr.p, keys_in.p);
-            SQGR_HIP(hipGetLastError());
-            SQGR_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys_in.p, keys_out.p, g.w.p, sw_out.p, (size_t)nnz, 0, 64, st));
-            SQGR_TRY(ensure_temp(tb));
-            {
-                LaunchTimer t(ctx, "mleiden_sort");
-                SQGR_HIP(rocprim::radix_sort_pairs(temp.p, tb, keys_in.p, keys_out.p, g.w.p, sw_out.p, (size_t)nnz, 0, 64, st));
-            }
-            SQGR_HIP(rocprim::reduce_by_key(nullptr, tb, keys_out.p, sw_out.p, (size_t)nnz, ukeys.p, out.w.p, n_unique.p, rocprim::plus<int64_t>(),
-                                            rocprim::equal_to<uint64_t>(), st));
-            SQGR_TRY(ensure_temp(tb));
-            {
-                LaunchTimer t(ctx, "mleiden_reduce");
-                SQGR_HIP(rocprim::reduce_by_key(temp.p, tb, keys_out.p, sw_out.p, (size_t)nnz, ukeys.p, out.w.p, n_unique.p,
-                                                rocprim::plus<int64_t>(), rocprim::equal_to<uint64_t>(), st));
-            }
-            SQGR_HIP(hipMemcpyAsync(&m, n_unique.p, 8, hipMemcpyDeviceToHost, st));
-            SQGR_HIP(hipStreamSynchronize(st));
-            if (m < 0 || m > nnz) {
-                set_error("sqgr_leiden_multiplex: reduce_by_key returned %lld groups of %lld entries", (long long)m, (long long)nnz);
-                return SQGR_ERR_HIP;
-            }
-            k_coarse_cols<<<blocks(m), LD_T, 0, st>>>(m, ukeys.p, out.indices.p);
-            SQGR_HIP(hipGetLastError());
-        }
-        k_coarse_indptr<<<blocks(nc + 1), LD_T, 0, st>>>(nc, m, ukeys.p, out.indptr.p);  // m == 0: every row is empty
-        SQGR_HIP(hipGetLastError());
-        out.n = nc;
-        out.nnz = m;
-        return SQGR_OK;
-    }
-
-    // the refined communities of level g become the nodes of `out`; *n_coarse == g.n: nothing merged and `out` is not built
-    int aggregate(const MxLevelBuf& g, MxLevelBuf& out, int64_t* n_coarse) {
-        const int64_t n = g.n;
-        SQGR_HIP(hipMemsetAsync(flags.p, 0, (size_t)n * 4, st));
-        k_flag<<<blocks(n), LD_T, 0, st>>>(n, rcomm.p, flags.p);
-        SQGR_HIP(hipGetLastError());
-        size_t tb = 0;
-        SQGR_HIP(rocprim::exclusive_scan(nullptr, tb, flags.p, newid.p, 0, (size_t)n, rocprim::plus<int32_t>(), st));
-        SQGR_TRY(ensure_temp(tb));
-        {
-            LaunchTimer t(ctx, "mleiden_renumber");
-            SQGR_HIP(rocprim::exclusive_scan(temp.p, tb, flags.p, newid.p, 0, (size_t)n, rocprim::plus<int32_t>(), st));
-        }
-        int32_t last[2];
-        SQGR_HIP(hipMemcpyAsync(&last[0], newid.p + (n - 1), 4, hipMemcpyDeviceToHost, st));
-        SQGR_HIP(hipMemcpyAsync(&last[1], flags.p + (n - 1), 4, hipMemcpyDeviceToHost, st));
-        SQGR_HIP(hipStreamSynchronize(st));
-        const int64_t nc = (int64_t)last[0] + last[1];
-        *n_coarse = nc;
-        if (nc == n) return SQGR_OK;
-        SQGR_HIP(hipMemsetAsync(pmin.p, 0x7f, (size_t)n * 4, st));
-        k_relabel<<<blocks(n), LD_T, 0, st>>>(n, rcomm.p, newid.p, comm.p, nr.p, pmin.p);
-        SQGR_HIP(hipGetLastError());
-        k_coarse_comm<<<blocks(n), LD_T, 0, st>>>(n, nr.p, comm.p, pmin.p, ccomm.p);
-        SQGR_HIP(hipGetLastError());
-        k_compose<<<blocks(n0), LD_T, 0, st>>>(n0, nr.p, node_of.p);
-        SQGR_HIP(hipGetLastError());
-        for (int l = 0; l < MX_LAYERS; ++l) SQGR_TRY(coarse_layer(g.l[l], out.l[l], nc));
-        out.n = nc;
-        return SQGR_OK;
-    }
-
-    // one iteration from comm (level 0 ids); leaves node_of
-    int iterate() {
-        k_iota<<<blocks(n0), LD_T, 0, st>>>(n0, node_of.p);
-        SQGR_HIP(hipGetLastError());
-        MxLevelBuf* cur = &g0;
-        for (;;) {
-            ++stat_levels;
-            Acc h[MX_LAYERS];
-            SQGR_TRY(prepare(*cur, h));
-            SQGR_TRY(rebuild_tot(*cur));
-            SQGR_TRY(local_moving(*cur));
-            int64_t kp = 0;
-            SQGR_TRY(count_distinct(cur->n, comm.p, &kp));
-            if (kp == cur->n) break;
-            SQGR_TRY(refine(*cur));
-            MxLevelBuf* next = cur == &ga ? &gb : &ga;
-            int64_t nc = 0;
-            SQGR_TRY(aggregate(*cur, *next, &nc));
-            if (nc == cur->n) break;
-            SQGR_HIP(hipMemcpyAsync(comm.p, ccomm.p, (size_t)nc * 4, hipMemcpyDeviceToDevice, st));
-            cur = next;
-        }
-        return SQGR_OK;
+            part[l] = d.two_m[l] ? (double)d.two_m[l] * ld_quality(h[l].sum_in, ld_join_sq(h[l]), d.gamma[l], d.two_m[l]) : 0.0;
+        return mx_mix(params(d), part[0], part[1]);
     }
 };
 
@@ -587,7 +364,7 @@ int sqgr_leiden_multiplex_info(int64_t* out_info) {
     out_info[2] = LD_ITER_CAP;
     out_info[3] = LD_CAP;
     out_info[4] = LD_SLOTS;
-    out_info[5] = MX_STATS;  // entries of out_stats
+    out_info[5] = ld_n_stats(MX_LAYERS);  // entries of out_stats
     out_info[6] = MX_LAYERS;
     return SQGR_OK;
 }
@@ -595,154 +372,9 @@ int sqgr_leiden_multiplex_info(int64_t* out_info) {
 int sqgr_leiden_multiplex(sqgr_ctx* ctx, int64_t n, const int64_t* indptr0, const int32_t* indices0, const int32_t* weights0,
                           const int64_t* indptr1, const int32_t* indices1, const int32_t* weights1, double resolution0, double resolution1,
                           double layer_ratio, int32_t n_iterations, int32_t* out_labels, int64_t* out_stats) {
-    SQGR_REQUIRE(ctx && indptr0 && indptr1 && out_labels && out_stats, "null argument");
-    SQGR_REQUIRE(n >= 1, "sqgr_leiden_multiplex: n=%lld", (long long)n);
-    SQGR_REQUIRE(std::isfinite(resolution0) && resolution0 > 0, "sqgr_leiden_multiplex: layer 0: resolution=%g must be finite and positive", resolution0);
-    SQGR_REQUIRE(std::isfinite(resolution1) && resolution1 > 0, "sqgr_leiden_multiplex: layer 1: resolution=%g must be finite and positive", resolution1);
-    SQGR_REQUIRE(std::isfinite(layer_ratio) && layer_ratio > 0, "sqgr_leiden_multiplex: layer_ratio=%g must be finite and positive", layer_ratio);
-    SQGR_REQUIRE(n_iterations != 0, "sqgr_leiden_multiplex: n_iterations=0 (a positive count, or negative for: until an iteration changes nothing)");
-    if (n >= ((int64_t)1 << 31) - 1) {
-        set_error("sqgr_leiden_multiplex: n=%lld, vertex ids are 32-bit", (long long)n);
-        return SQGR_ERR_UNSUPPORTED;
-    }
     const int64_t* const indptr[MX_LAYERS] = {indptr0, indptr1};
     const int32_t* const indices[MX_LAYERS] = {indices0, indices1};
     const int32_t* const weights[MX_LAYERS] = {weights0, weights1};
-    int64_t nnz[MX_LAYERS];
-    for (int l = 0; l < MX_LAYERS; ++l) {
-        SQGR_REQUIRE(indptr[l][0] == 0, "sqgr_leiden_multiplex: layer %d: indptr[0]=%lld", l, (long long)indptr[l][0]);
-        for (int64_t i = 0; i < n; ++i)
-            SQGR_REQUIRE(indptr[l][i + 1] >= indptr[l][i], "sqgr_leiden_multiplex: layer %d: indptr decreases at row %lld", l, (long long)i);
-        nnz[l] = indptr[l][n];
-        SQGR_REQUIRE(nnz[l] == 0 || (indices[l] && weights[l]), "null argument");
-        if (nnz[l] >= ((int64_t)1 << 36)) {
-            set_error("sqgr_leiden_multiplex: layer %d: nnz=%lld", l, (long long)nnz[l]);
-            return SQGR_ERR_UNSUPPORTED;
-        }
-    }
-    for (int i = 0; i < MX_STATS; ++i) out_stats[i] = 0;
-    if (nnz[0] + nnz[1] == 0) {  // 2m_0 = 2m_1 = 0: every vertex is its own community
-        for (int64_t i = 0; i < n; ++i) out_labels[i] = (int32_t)i;
-        out_stats[0] = n;
-        out_stats[9] = 1;
-        return SQGR_OK;
-    }
-    SQGR_HIP(hipSetDevice(ctx->device));
-    Multiplex S;
-    S.ctx = ctx;
-    S.st = ctx->stream;
-    S.grid = 8u * (unsigned)std::max(ctx->cu_count, 1);
-    S.P.gamma[0] = resolution0;
-    S.P.gamma[1] = resolution1;
-    S.P.ratio = layer_ratio;
-    S.n0 = n;
-    hipStream_t st = S.st;
-    const size_t ncap = (size_t)n;
-    size_t ecap_max = 0;
-    for (int l = 0; l < MX_LAYERS; ++l) {  // a coarse level has fewer nodes and at most one self loop per node more
-        S.ecap[l] = nnz[l] + n;
-        ecap_max = std::max(ecap_max, (size_t)S.ecap[l]);
-        SQGR_TRY(S.g0.l[l].alloc(n, nnz[l]));
-        SQGR_TRY(S.ga.l[l].alloc(n, S.ecap[l]));
-        SQGR_TRY(S.gb.l[l].alloc(n, S.ecap[l]));
-        for (DevBuf<int64_t>* b : {&S.tot[l], &S.dk[l], &S.rtot[l], &S.rext[l], &S.vext[l], &S.mk_best[l], &S.mtot_target[l]}) SQGR_TRY(b->alloc(ncap));
-        SQGR_TRY(S.mclaimed[l].alloc(ncap));
-    }
-    for (DevBuf<int32_t>* b : {&S.comm, &S.best_comm, &S.want, &S.rcomm, &S.rsize, &S.flags, &S.newid, &S.nr, &S.pmin, &S.ccomm, &S.node_of, &S.long_rows})
-        SQGR_TRY(b->alloc(ncap));
-    SQGR_TRY(S.mg_own.alloc(ncap));
-    SQGR_TRY(S.mfirst.alloc(ncap));
-    SQGR_TRY(S.sw_out.alloc(ecap_max));
-    SQGR_TRY(S.keys_in.alloc(ecap_max));
-    SQGR_TRY(S.keys_out.alloc(ecap_max));
-    SQGR_TRY(S.ukeys.alloc(ecap_max));
-    SQGR_TRY(S.acc.alloc(MX_LAYERS));
-    SQGR_TRY(S.n_unique.alloc(1));
-    SQGR_HIP(hipMemsetAsync(S.acc.p, 0, MX_LAYERS * sizeof(Acc), st));
-
-    // upload and check
-    DevBuf<int32_t> w32[MX_LAYERS];
-    DevBuf<int> flags;
-    SQGR_TRY(flags.alloc(5 * MX_LAYERS));
-    SQGR_HIP(hipMemsetAsync(flags.p, 0, 5 * MX_LAYERS * sizeof(int), st));
-    S.g0.n = n;
-    for (int l = 0; l < MX_LAYERS; ++l) {
-        LevelBuf& g = S.g0.l[l];
-        g.n = n;
-        g.nnz = nnz[l];
-        SQGR_TRY(w32[l].alloc((size_t)nnz[l]));
-        SQGR_HIP(hipMemcpyAsync(g.indptr.p, indptr[l], ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
-        if (!nnz[l]) continue;
-        SQGR_HIP(hipMemcpyAsync(g.indices.p, indices[l], (size_t)nnz[l] * 4, hipMemcpyHostToDevice, st));
-        SQGR_HIP(hipMemcpyAsync(w32[l].p, weights[l], (size_t)nnz[l] * 4, hipMemcpyHostToDevice, st));
-        k_widen<<<S.blocks(nnz[l]), LD_T, 0, st>>>(w32[l].p, nnz[l], g.w.p);
-        SQGR_HIP(hipGetLastError());
-    }
-    Acc hacc[MX_LAYERS];
-    SQGR_TRY(S.prepare(S.g0, hacc));  // erow (indptr alone decides it), k, 2m
-    for (int l = 0; l < MX_LAYERS; ++l) {
-        if (!nnz[l]) continue;
-        LaunchTimer t(ctx, "mleiden_check");
-        k_check<<<S.blocks(nnz[l]), LD_T, 0, st>>>(n, S.g0.l[l].indptr.p, S.g0.l[l].indices.p, w32[l].p, S.g0.l[l].erow.p, nnz[l], flags.p + 5 * l);
-        SQGR_HIP(hipGetLastError());
-    }
-    int hf[5 * MX_LAYERS];
-    for (int& f : hf) f = 1;
-    SQGR_HIP(hipMemcpyAsync(hf, flags.p, sizeof(hf), hipMemcpyDeviceToHost, st));
-    SQGR_HIP(hipStreamSynchronize(st));
-    for (int l = 0; l < MX_LAYERS; ++l) {
-        const int* f = hf + 5 * l;
-        SQGR_REQUIRE(!f[4], "sqgr_leiden_multiplex: layer %d: a column index is outside [0, n)", l);
-        SQGR_REQUIRE(!f[3], "sqgr_leiden_multiplex: layer %d: a weight is smaller than 1", l);
-        SQGR_REQUIRE(!f[1], "sqgr_leiden_multiplex: layer %d: a row of the graph is not sorted or repeats an entry", l);
-        SQGR_REQUIRE(!f[2], "sqgr_leiden_multiplex: layer %d: the graph has a self loop", l);
-        SQGR_REQUIRE(!f[0], "sqgr_leiden_multiplex: layer %d: the graph is not symmetric (an entry without a mirror entry of equal weight)", l);
-        const unsigned __int128 two_m128 = (unsigned __int128)hacc[l].two_m[0] + ((unsigned __int128)hacc[l].two_m[1] << 32);
-        if (two_m128 >= ((unsigned __int128)1 << 62)) {
-            set_error("sqgr_leiden_multiplex: layer %d: the sum of all weights reaches 2^62", l);
-            return SQGR_ERR_UNSUPPORTED;
-        }
-        S.two_m[l] = (int64_t)two_m128;
-        S.P.two_m[l] = (double)S.two_m[l];
-    }
-
-    std::vector<int32_t> ids((size_t)n), labels((size_t)n), prev((size_t)n);
-    std::iota(prev.begin(), prev.end(), 0);  // the start: every vertex alone, which is canonical
-    const int max_it = n_iterations < 0 ? LD_ITER_CAP : n_iterations;
-    int64_t K = n, iterations = 0, settled = 0;
-    for (int it = 0; it < max_it; ++it) {
-        SQGR_HIP(hipMemcpyAsync(S.comm.p, prev.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-        SQGR_TRY(S.iterate());
-        SQGR_HIP(hipMemcpyAsync(ids.data(), S.node_of.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        SQGR_HIP(hipStreamSynchronize(st));
-        const int64_t k_new = canonical_labels(ids, n, labels.data());
-        ++iterations;
-        if (labels == prev) {
-            settled = 1;
-            break;
-        }
-        prev.swap(labels);
-        K = k_new;
-    }
-    // sum_c in^l_c of the result on the input layers
-    SQGR_HIP(hipMemcpyAsync(S.comm.p, prev.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-    for (int l = 0; l < MX_LAYERS; ++l) {
-        SQGR_HIP(hipMemsetAsync(&S.acc.p[l].sum_in, 0, 8, st));
-        if (!nnz[l]) continue;
-        k_sum_in<<<S.blocks(nnz[l]), LD_T, 0, st>>>(nnz[l], S.g0.l[l].erow.p, S.g0.l[l].indices.p, S.g0.l[l].w.p, S.comm.p, &S.acc.p[l]);
-        SQGR_HIP(hipGetLastError());
-    }
-    SQGR_TRY(S.read_acc(hacc));
-    std::copy(prev.begin(), prev.end(), out_labels);
-    out_stats[0] = K;
-    out_stats[1] = iterations;
-    out_stats[2] = S.stat_levels;
-    out_stats[3] = S.stat_sweeps;
-    out_stats[4] = hacc[0].sum_in;
-    out_stats[5] = S.two_m[0];
-    out_stats[6] = hacc[1].sum_in;
-    out_stats[7] = S.two_m[1];
-    out_stats[8] = S.stat_cap_hits;
-    out_stats[9] = settled;
-    return SQGR_OK;
+    const double resolution[MX_LAYERS] = {resolution0, resolution1};
+    return leiden_run<MX_LAYERS, TwoLayers>(ctx, n, indptr, indices, weights, resolution, layer_ratio, n_iterations, out_labels, out_stats);
 }
