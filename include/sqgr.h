@@ -610,6 +610,32 @@ int sqgr_leiden_multiplex(sqgr_ctx* ctx, int64_t n, const int64_t* indptr0, cons
                           const int64_t* indptr1, const int32_t* indices1, const int32_t* weights1, double resolution0, double resolution1,
                           double layer_ratio, int32_t n_iterations, int32_t* out_labels, int64_t* out_stats);
 
+/* ---- mask_graph: `LineString([a_k, b_k]).within(polygon_mask)` for every edge of a spatial graph (gr/_build.py:852-954), as the numpy
+ * restatement squidpy_amd/gr/_mask.py evaluates it: plain float64 cross products, divisions and comparisons, every operation rounded
+ * on its own (no FMA), IEEE division — the device returns that code's booleans bit for bit.
+ *
+ * sqgr_mask_info: out_info int64[2] = {cut parameters of one segment held on chip (0 and 1 included), (point or segment, ring edge)
+ *   pairs of one kernel launch}.  Needs no device.
+ * sqgr_segments_within: HOST arrays.  a_xy, b_xy float64[E][2]: the segments' ends.  ring_xy float64[P][2]: all rings concatenated as
+ *   closed coordinate lists (first point == last point, at least 4 stored points each); ring_offsets int64[n_rings + 1]: ring r is
+ *   points [ring_offsets[r], ring_offsets[r + 1]), ring_offsets[0] = 0; ring_polygon int32[n_rings]: the polygon of every ring,
+ *   counting up from 0, a polygon's rings contiguous and its first ring the shell, the others holes.  Crossing parity is kept per
+ *   ring: a point is in a hole when it is inside ANY hole of the polygon.  SQGR_ERR_INVALID for a ring that is not closed or shorter,
+ *   ids out of order, E or the number of ring edges R >= 2^31, or a coordinate that is not finite.  E = 0 is valid.
+ *   out_within uint8[E]: 0, 1, or 2 = overflow: the segment is cut (touches a ring, neither end outside) and would produce more cut
+ *   parameters — 0, 1, one per crossing, two per collinear ring edge — than the first entry of sqgr_mask_info; the caller recomputes
+ *   such a row on the host.  out_stats int64[4] = {touched segments, cut segments (overflowed ones included), overflow, launches of
+ *   the kernels that walk the ring edges}.  Brute force over the ring edges: E R pair tests and 3 E R point-edge tests, cut into
+ *   launches of at most the second entry of sqgr_mask_info pairs.  Two calls return the same bytes.
+ * sqgr_segments_within_hook (parity hook): the same with pairs_per_launch (0 = the default) and, when out_classes is not NULL,
+ *   out_classes uint8[3][E] = the classes of a, b and 0.5 (a + b): 0 outside, 1 on a boundary, 2 inside (`_classify`). */
+int sqgr_mask_info(int64_t* out_info);
+int sqgr_segments_within(sqgr_ctx* ctx, const double* a_xy, const double* b_xy, int64_t E, const double* ring_xy, const int64_t* ring_offsets,
+                         const int32_t* ring_polygon, int64_t n_rings, uint8_t* out_within, int64_t* out_stats);
+int sqgr_segments_within_hook(sqgr_ctx* ctx, const double* a_xy, const double* b_xy, int64_t E, const double* ring_xy,
+                              const int64_t* ring_offsets, const int32_t* ring_polygon, int64_t n_rings, uint8_t* out_within, int64_t* out_stats,
+                              int64_t pairs_per_launch, uint8_t* out_classes);
+
 #ifdef __cplusplus
 }
 #endif

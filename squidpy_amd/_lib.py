@@ -134,6 +134,10 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "sqgr_leiden_multiplex_info": (C.c_int, [c_i64p]),
     "sqgr_leiden_multiplex": (C.c_int, [C.c_void_p, C.c_int64, c_i64p, c_i32p, c_i32p, c_i64p, c_i32p, c_i32p, C.c_double, C.c_double, C.c_double,
                                         C.c_int32, c_i32p, c_i64p]),
+    "sqgr_mask_info": (C.c_int, [c_i64p]),
+    "sqgr_segments_within": (C.c_int, [C.c_void_p, c_f64p, c_f64p, C.c_int64, c_f64p, c_i64p, c_i32p, C.c_int64, c_u8p, c_i64p]),
+    "sqgr_segments_within_hook": (C.c_int, [C.c_void_p, c_f64p, c_f64p, C.c_int64, c_f64p, c_i64p, c_i32p, C.c_int64, c_u8p, c_i64p,
+                                            C.c_int64, c_u8p]),
 }
 
 
@@ -1430,3 +1434,41 @@ class DevicePoints:
             self.close()
         except Exception:
             pass
+
+
+def mask_info() -> dict[str, int]:
+    """The constants of the mask kernels (``sqgr_mask_info``); needs no device."""
+    lib = load_library()
+    v = np.zeros(2, dtype=np.int64)
+    _check(lib, lib.sqgr_mask_info(_ptr(v, c_i64p)))
+    return {"param_cap": int(v[0]), "pairs_per_launch": int(v[1])}
+
+
+def segments_within(
+    ctx: Context, a: np.ndarray, b: np.ndarray, ring_xy: np.ndarray, ring_offsets: np.ndarray, ring_polygon: np.ndarray,
+    pairs_per_launch: int = 0, return_classes: bool = False,
+) -> tuple[np.ndarray, dict[str, int], np.ndarray | None]:
+    """``LineString([a_k, b_k]).within(polygon)`` on the device (``sqgr_segments_within``) -> ``(within uint8 (E,): 0, 1, or 2 = the
+    segment has more cut parameters than the kernels hold, stats, classes)``.  The rings are closed coordinate lists, concatenated;
+    ``ring_polygon[r]`` is the polygon of ring ``r`` and a polygon's first ring its shell.  ``pairs_per_launch`` (0: the library's) and
+    ``return_classes`` (uint8 (3, E): the classes of a, b and the midpoints) go through the parity hook."""
+    a, b = _as(a, np.float64).reshape(-1, 2), _as(b, np.float64).reshape(-1, 2)
+    if a.shape != b.shape:
+        raise ValueError(f"Expected as many segment starts as ends, found {a.shape} and {b.shape}.")
+    ring_xy = _as(ring_xy, np.float64).reshape(-1, 2)
+    ring_offsets, ring_polygon = _as(ring_offsets, np.int64), _as(ring_polygon, np.int32)
+    if len(ring_offsets) != len(ring_polygon) + 1 or (len(ring_offsets) and ring_offsets[-1] != len(ring_xy)):
+        raise ValueError("`ring_offsets` must hold one entry per ring plus the number of stored points.")
+    e = len(a)
+    out = np.zeros(e, dtype=np.uint8)
+    stats = np.zeros(4, dtype=np.int64)
+    classes = np.zeros((3, e), dtype=np.uint8) if return_classes else None
+    if pairs_per_launch or return_classes:
+        rc = ctx.lib.sqgr_segments_within_hook(ctx.h, _ptr(a, c_f64p), _ptr(b, c_f64p), e, _ptr(ring_xy, c_f64p), _ptr(ring_offsets, c_i64p),
+                                               _ptr(ring_polygon, c_i32p), len(ring_polygon), _ptr(out, c_u8p), _ptr(stats, c_i64p),
+                                               int(pairs_per_launch), _ptr(classes, c_u8p))
+    else:
+        rc = ctx.lib.sqgr_segments_within(ctx.h, _ptr(a, c_f64p), _ptr(b, c_f64p), e, _ptr(ring_xy, c_f64p), _ptr(ring_offsets, c_i64p),
+                                          _ptr(ring_polygon, c_i32p), len(ring_polygon), _ptr(out, c_u8p), _ptr(stats, c_i64p))
+    _check(ctx.lib, rc)
+    return out, dict(zip(("touched", "cut", "overflow", "launches"), (int(v) for v in stats))), classes

@@ -9,7 +9,11 @@ segment lies in the polygon's open interior.  Evaluated exactly in that form: th
 meets a ring edge, and the midpoint of every piece (and both end points) is classified as inside / on the boundary / outside.
 Parity note: the arithmetic is plain float64 cross products, GEOS uses exact predicates — the two agree unless a graph edge
 touches the polygon boundary to within rounding; the reference's own test (tests/graph/test_spatial_neighbors.py:388-456)
-is ported in tests/test_mask_graph_cpu.py."""
+is ported in tests/test_mask_graph_cpu.py.
+
+``device="host"`` (the default) runs the numpy code below.  ``device=None`` or a device index runs the same predicate on the GPU
+(``csrc/sqgr_mask.hip``: the expressions of :func:`_classify` and :func:`segments_within` operation for operation, so the answer is
+the host's bit for bit); without a usable device that raises, it never falls back to the host."""
 
 from __future__ import annotations
 
@@ -103,11 +107,46 @@ def _classify(pts: np.ndarray, polys: list[list[np.ndarray]]) -> np.ndarray:
     return best
 
 
-def segments_within(a: np.ndarray, b: np.ndarray, polygon_mask: Any, chunk: int = 65536) -> np.ndarray:
-    """``LineString([a_k, b_k]).within(polygon_mask)`` for every row k (see the module docstring)."""
+def _flat_rings(polys: list[list[np.ndarray]]) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """What the device takes: all rings concatenated as closed coordinate lists, the ring offsets, the polygon of every ring."""
+    rings = [r for rs in polys for r in rs]
+    ring_xy = np.ascontiguousarray(np.concatenate(rings), dtype=np.float64)
+    ring_offsets = np.concatenate([[0], np.cumsum([len(r) for r in rings])]).astype(np.int64)
+    ring_polygon = np.repeat(np.arange(len(polys), dtype=np.int32), [len(rs) for rs in polys])
+    return ring_xy, ring_offsets, ring_polygon
+
+
+def segments_within(
+    a: np.ndarray, b: np.ndarray, polygon_mask: Any, chunk: int = 65536, *, device: int | str | None = "host", return_stats: bool = False
+) -> Any:
+    """``LineString([a_k, b_k]).within(polygon_mask)`` for every row k (see the module docstring).
+
+    ``device="host"``: numpy.  ``device=None`` / an index: the kernels on ``default_context(device)``; a row whose cut parameters pass
+    the kernels' capacity (``_lib.mask_info()``) comes back marked and is recomputed by the host code — the only host recomputation,
+    counted in ``stats["overflow"]``.  ``return_stats=True`` also returns ``{"touched", "cut", "overflow", "launches"}``: segments that
+    meet a ring, those of them with neither end outside (cut into pieces), rows recomputed on the host, kernel launches over the rings."""
     polys = _polygons(polygon_mask)
     a = np.asarray(a, dtype=np.float64).reshape(-1, 2)
     b = np.asarray(b, dtype=np.float64).reshape(-1, 2)
+    stats = {"touched": 0, "cut": 0, "overflow": 0, "launches": 0}
+    if isinstance(device, str):
+        if device != "host":
+            raise ValueError(f"`device` should be 'host', None or a device index, got {device!r}")
+        out = _segments_within_host(a, b, polys, chunk, stats)
+    else:
+        from .. import _lib
+
+        if not (np.isfinite(a).all() and np.isfinite(b).all() and all(np.isfinite(r).all() for rs in polys for r in rs)):
+            raise ValueError("The device path needs finite coordinates.")
+        code, stats, _ = _lib.segments_within(_lib.default_context(device), a, b, *_flat_rings(polys))
+        out = code == 1
+        over = np.nonzero(code == 2)[0]
+        if len(over):
+            out[over] = _segments_within_host(a[over], b[over], polys, chunk)
+    return (out, stats) if return_stats else out
+
+
+def _segments_within_host(a: np.ndarray, b: np.ndarray, polys: list[list[np.ndarray]], chunk: int, stats: dict | None = None) -> np.ndarray:
     edges = np.concatenate([np.stack([r[:-1], r[1:]], axis=1) for rings in polys for r in rings])  # (R, 2, 2)
     p, q = edges[:, 0], edges[:, 1]
     out = np.zeros(len(a), dtype=bool)
@@ -128,6 +167,9 @@ def segments_within(a: np.ndarray, b: np.ndarray, polygon_mask: Any, chunk: int 
         # parallel and collinear: the ring edge's end points projected on the segment
         col = (den == 0) & (_cross(wx, wy, dx, dy) == 0)
         touched = hit.any(axis=1) | col.any(axis=1)
+        if stats is not None:
+            stats["touched"] += int(touched.sum())
+            stats["cut"] += int((touched & (ca != 0) & (cb != 0)).sum())
         res = np.zeros(n, dtype=bool)
         # no contact with any ring: the whole segment has the class of its midpoint
         free = ~touched
@@ -154,6 +196,13 @@ def segments_within(a: np.ndarray, b: np.ndarray, polygon_mask: Any, chunk: int 
     return out
 
 
+def _csr_filter(m: sparse.csr_matrix, keep: np.ndarray) -> sparse.csr_matrix:
+    """``m`` without the stored entries where ``keep`` is False."""
+    rows = np.repeat(np.arange(m.shape[0]), np.diff(m.indptr))
+    indptr = np.concatenate([[0], np.cumsum(np.bincount(rows[keep], minlength=m.shape[0]))])
+    return sparse.csr_matrix((m.data[keep], m.indices[keep], indptr), shape=m.shape)
+
+
 def mask_graph(
     sdata: Any,
     table_key: str,
@@ -162,13 +211,19 @@ def mask_graph(
     spatial_key: str = Key.obsm.spatial,
     key_added: str = "mask",
     copy: bool = False,
+    *,
+    device: int | str | None = "host",
 ) -> tuple[sparse.csr_matrix, sparse.csr_matrix] | None:
     """Mask the graph based on a polygon mask (drop-in for ``squidpy.gr.mask_graph``, gr/_build.py:852-954).
 
     Only the edges fully contained in the polygon(s) are kept (``negative_mask=True``: only those are removed).  Reads
     ``obsp['{spatial_key}_connectivities' | '{spatial_key}_distances']`` and ``obsm[spatial_key]`` of the table; ``copy=True``
     returns ``(connectivities, distances)``, otherwise writes ``obsp['{key_added}_{spatial_key}_connectivities']``,
-    ``obsp['{key_added}_{spatial_key}_distances']`` and ``uns['{key_added}_{spatial_key}_neighbors']`` like the reference."""
+    ``obsp['{key_added}_{spatial_key}_distances']`` and ``uns['{key_added}_{spatial_key}_neighbors']`` like the reference.
+
+    ``device="host"`` (the default) evaluates the predicate with numpy; ``device=None`` or a device index evaluates it on the GPU
+    (:func:`segments_within`) and, where both matrices are canonical CSR, drops the edges by a filter over the CSR arrays instead of
+    through ``tolil()``.  The result is the host path's.  Without a usable device that raises ``SqgrError``."""
     neighs_key = Key.uns.spatial_neighs(spatial_key)
     conns_key = Key.obsp.spatial_conn(spatial_key)
     dists_key = Key.obsp.spatial_dist(spatial_key)
@@ -180,10 +235,16 @@ def mask_graph(
     dst = sparse.csr_matrix(table.obsp[dists_key]).copy()
     rows = np.repeat(np.arange(adj.shape[0]), np.diff(adj.indptr))
     cols = adj.indices
-    within = segments_within(coords[rows, :2], coords[cols, :2], polygon_mask)
+    within = segments_within(coords[rows, :2], coords[cols, :2], polygon_mask, device=device)
     drop = within if negative_mask else ~within
     r, c = rows[drop], cols[drop]
-    if len(r):
+    if len(r) and not isinstance(device, str) and adj.has_canonical_format and dst.has_canonical_format:
+        # sorted rows without duplicates: an entry is its (row, col) key, and dropping entries keeps the format
+        adj = _csr_filter(adj, ~drop)
+        key = r.astype(np.int64) * dst.shape[1] + c
+        dst_rows = np.repeat(np.arange(dst.shape[0], dtype=np.int64), np.diff(dst.indptr))
+        dst = _csr_filter(dst, ~np.isin(dst_rows * dst.shape[1] + dst.indices, key))
+    elif len(r):
         adj = adj.tolil()
         dst = dst.tolil()
         adj[r, c] = 0
