@@ -636,6 +636,32 @@ int sqgr_segments_within_hook(sqgr_ctx* ctx, const double* a_xy, const double* b
                               const int64_t* ring_offsets, const int32_t* ring_polygon, int64_t n_rings, uint8_t* out_within, int64_t* out_stats,
                               int64_t pairs_per_launch, uint8_t* out_classes);
 
+/* ---- var_by_distance: the distance from every observation to the nearest member of each anchor set (tl/_var_by_distance.py:129-134,
+ * one sklearn KDTree per (anchor, slide) queried with every observation of the slide) — all anchors and all slides in one call.
+ * Float64, no FMA, sklearn's order of operations: euclidean sqrt(min((dx*dx + dy*dy) + dz*dz)) with one correctly rounded square
+ * root at the end, manhattan min((|dx| + |dy|) + |dz|), chebyshev min(max |d|) — KDTree.query's distances bit for bit.
+ *
+ * sqgr_anchor_dist_info: out_info int64[5] = {points below which a set is one cell (swept whole), target points per cell, largest
+ *   dim, most anchor columns of a call, threads of a query block}.  Needs no device.
+ * sqgr_anchor_dist: HOST arrays.  q float64[nq][dim] row-major, dim 2 or 3; q_slide int32[nq]: the slide of every query, -1 = no
+ *   result; r float64[nr][dim]: the reference points of all sets, in any order; r_set int32[nr]: the set of each; set_of
+ *   int32[n_anchors][n_slides]: the set that anchor column a searches for a query of slide s, or -1; set ids are
+ *   0 .. n_anchors * n_slides - 1 and a set may serve several pairs.  metric: 0 euclidean, 1 manhattan, 2 chebyshev.
+ *   out float64[n_anchors][nq]: out[a][i] = min over j with r_set[j] == set_of[a][q_slide[i]] of the metric distance; NaN when the
+ *   query has no slide, the pair has no set, or the set has no point.  Every set gets a uniform cell grid built on the device; one
+ *   launch of the query kernel serves all (query, anchor column) pairs.  out_stats int64[4] = {cells of all grids, sets with more
+ *   than one cell, launches of the query kernel, reference points}.  Two calls return the same bytes.  SQGR_ERR_INVALID for a
+ *   coordinate that is not finite, dim other than 2 or 3, a slide or set id out of range, nq or nr >= 2^31 - 1, nq < 1, more than the
+ *   fourth entry of sqgr_anchor_dist_info anchor columns.
+ * sqgr_anchor_dist_hook (parity hook, tuning): the same with the one-cell threshold and the target points per cell given (0 = the
+ *   defaults). */
+int sqgr_anchor_dist_info(int64_t* out_info);
+int sqgr_anchor_dist(sqgr_ctx* ctx, int32_t dim, const double* q, const int32_t* q_slide, int64_t nq, const double* r, const int32_t* r_set,
+                     int64_t nr, const int32_t* set_of, int32_t n_anchors, int32_t n_slides, int32_t metric, double* out, int64_t* out_stats);
+int sqgr_anchor_dist_hook(sqgr_ctx* ctx, int32_t dim, const double* q, const int32_t* q_slide, int64_t nq, const double* r, const int32_t* r_set,
+                          int64_t nr, const int32_t* set_of, int32_t n_anchors, int32_t n_slides, int32_t metric, double* out, int64_t* out_stats,
+                          int64_t brute_below, double target_per_cell);
+
 #ifdef __cplusplus
 }
 #endif

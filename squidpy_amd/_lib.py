@@ -138,6 +138,11 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "sqgr_segments_within": (C.c_int, [C.c_void_p, c_f64p, c_f64p, C.c_int64, c_f64p, c_i64p, c_i32p, C.c_int64, c_u8p, c_i64p]),
     "sqgr_segments_within_hook": (C.c_int, [C.c_void_p, c_f64p, c_f64p, C.c_int64, c_f64p, c_i64p, c_i32p, C.c_int64, c_u8p, c_i64p,
                                             C.c_int64, c_u8p]),
+    "sqgr_anchor_dist_info": (C.c_int, [c_i64p]),
+    "sqgr_anchor_dist": (C.c_int, [C.c_void_p, C.c_int32, c_f64p, c_i32p, C.c_int64, c_f64p, c_i32p, C.c_int64, c_i32p, C.c_int32, C.c_int32,
+                                   C.c_int32, c_f64p, c_i64p]),
+    "sqgr_anchor_dist_hook": (C.c_int, [C.c_void_p, C.c_int32, c_f64p, c_i32p, C.c_int64, c_f64p, c_i32p, C.c_int64, c_i32p, C.c_int32, C.c_int32,
+                                        C.c_int32, c_f64p, c_i64p, C.c_int64, C.c_double]),
 }
 
 
@@ -1472,3 +1477,49 @@ def segments_within(
                                           _ptr(ring_polygon, c_i32p), len(ring_polygon), _ptr(out, c_u8p), _ptr(stats, c_i64p))
     _check(ctx.lib, rc)
     return out, dict(zip(("touched", "cut", "overflow", "launches"), (int(v) for v in stats))), classes
+
+
+def anchor_dist_info() -> dict[str, int]:
+    """The constants of the anchor search (``sqgr_anchor_dist_info``); needs no device."""
+    lib = load_library()
+    v = np.zeros(5, dtype=np.int64)
+    _check(lib, lib.sqgr_anchor_dist_info(_ptr(v, c_i64p)))
+    return dict(zip(("brute_below", "per_cell", "max_dim", "max_anchors", "block"), (int(x) for x in v)))
+
+
+def anchor_distances(
+    ctx: Context, coords: np.ndarray, slide_codes: np.ndarray, ref_coords: np.ndarray, ref_sets: np.ndarray, set_of: np.ndarray,
+    metric: str = "euclidean", brute_below: int = 0, per_cell: float = 0.0, return_stats: bool = False,
+) -> Any:
+    """For every row of ``coords`` ((n, 2) or (n, 3)) and every anchor column ``a`` the ``metric`` distance to the nearest row of
+    ``ref_coords`` whose ``ref_sets`` entry is ``set_of[a, slide_codes[row]]`` -> float64 ``(n_anchors, n)``; NaN for a slide code of
+    -1, a ``set_of`` entry of -1 and a set without points (``sqgr_anchor_dist``: one call for all anchors and slides).
+    ``brute_below`` / ``per_cell`` (0: the library's) go through the hook; ``return_stats`` adds ``{cells, gridded_sets, launches,
+    ref_points}``."""
+    coords = _search_coords(coords)
+    ref_coords = _as(ref_coords, np.float64)
+    if ref_coords.ndim != 2 or ref_coords.shape[1] != coords.shape[1]:
+        raise ValueError(f"Expected reference coordinates of shape (m, {coords.shape[1]}), found {ref_coords.shape}.")
+    slide_codes, ref_sets, set_of = _as(slide_codes, np.int32), _as(ref_sets, np.int32), _as(set_of, np.int32)
+    n, m = coords.shape[0], ref_coords.shape[0]
+    if slide_codes.shape != (n,):
+        raise ValueError(f"Expected one slide code per row of the coordinates, found {slide_codes.shape} for {n} rows.")
+    if ref_sets.shape != (m,):
+        raise ValueError(f"Expected one set id per reference point, found {ref_sets.shape} for {m} points.")
+    if set_of.ndim != 2 or set_of.shape[0] < 1 or set_of.shape[1] < 1:
+        raise ValueError(f"Expected `set_of` of shape (n_anchors, n_slides), found {set_of.shape}.")
+    if metric not in METRICS or METRICS[metric] > 2:
+        raise ValueError(f"metric '{metric}' is not valid for KDTree")
+    out = np.empty((set_of.shape[0], n), dtype=np.float64)
+    stats = np.zeros(4, dtype=np.int64)
+    if n == 0:
+        return (out, dict(cells=0, gridded_sets=0, launches=0, ref_points=m)) if return_stats else out
+    args = (ctx.h, coords.shape[1], _ptr(coords, c_f64p), _ptr(slide_codes, c_i32p), n, _ptr(ref_coords, c_f64p), _ptr(ref_sets, c_i32p), m,
+            _ptr(set_of, c_i32p), set_of.shape[0], set_of.shape[1], METRICS[metric], _ptr(out, c_f64p), _ptr(stats, c_i64p))
+    if brute_below or per_cell:
+        _check(ctx.lib, ctx.lib.sqgr_anchor_dist_hook(*args, int(brute_below), float(per_cell)))
+    else:
+        _check(ctx.lib, ctx.lib.sqgr_anchor_dist(*args))
+    if return_stats:
+        return out, dict(zip(("cells", "gridded_sets", "launches", "ref_points"), (int(v) for v in stats)))
+    return out
