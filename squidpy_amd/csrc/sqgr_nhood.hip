@@ -27,6 +27,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 namespace sqgr {
@@ -825,21 +826,29 @@ __global__ __launch_bounds__(COUNT_THREADS) void k_count_global(int64_t nnz, con
 }
 
 // ---------------------------------------------------------------------------------------------- reduction
-// Partial histograms and accumulator slots of a batch are laid out [16 / pw planes][pair][pw]: slot j <-> permutation
+// Partial histograms of a batch are laid out [16 / pw planes][pair][pw]: slot j <-> permutation
 // b = (j / (K2 * pw)) * pw + j % pw of pair (j / pw) % K2 — pw = B (one plane, word = pair * B + b) for k_count and the
 // device-scope kernels, pw = the pass width for k_count_pass, whose blocks each write ONE contiguous plane (or, for K > 202,
-// one half of its rows).  acc slots are private to (batch, j): no atomics, bit-reproducible.
-// 256 threads = 64 slots x 4 slices of the block loop (combined through LDS).
+// one half of its rows).
+// SLICED: 256 threads = 64 slots x 4 slices of the block loop (combined through LDS).  The moments need one number per pair, not per
+// permutation: the pw lanes of a pair add their d and d*d up inside the wave and the first of them adds the sums to the ONE
+// accumulator slot acc[batch][plane][pair] — private to that lane: no atomics, bit-reproducible (integer sums, exact in any
+// order); K2 * B / pw slots per batch, the layout k_reduce16 keeps with one plane.
 // sym: bit 1 (value 2): the partials are in doubled units (half lists with self loops): count = sum / 2;
 //      bit 2 (value 4): the partials hold h of the half list, not h + h^T: the transposed pair's slot is added here (the
 //      pass kernel with split rows cannot form it in LDS).
+// SLICED = false (few partials per batch — the long launches, where this kernel is 36 000 blocks at 30 clusters): 256 threads =
+// 256 slots, every lane walks the partials itself — its loads are independent of each other, and no wave waits at a barrier for
+// three others to hand over two words each.
+constexpr int REDUCE_SLICED_FROM = 17;  // partials per batch from which four slices share the walk (reduce_batches)
+template <bool SLICED>
 __global__ __launch_bounds__(256) void k_reduce(const uint32_t* __restrict__ partial_all, int nblk, int nsum, int hist_words, int B, int pw,
                                                 int K, int sym, const int64_t* __restrict__ shift, int64_t perm_batch0,
                                                 int64_t perm_begin, int64_t perm_end, int64_t* __restrict__ acc_sum,
                                                 uint64_t* __restrict__ acc_sq, uint32_t* __restrict__ perms_out) {
-    __shared__ unsigned long long part[4][64];
-    const int wl = threadIdx.x & 63, slice = threadIdx.x >> 6;
-    const int j = blockIdx.x * 64 + wl;
+    __shared__ unsigned long long part[SLICED ? 4 : 1][64];
+    const int wl = threadIdx.x & 63, slice = SLICED ? threadIdx.x >> 6 : 0;
+    const int j = SLICED ? blockIdx.x * 64 + wl : blockIdx.x * 256 + (int)threadIdx.x;
     const int batch = blockIdx.y;
     const int K2 = K * K;
     int pair = 0, b = 0, jt = 0;
@@ -852,34 +861,62 @@ __global__ __launch_bounds__(256) void k_reduce(const uint32_t* __restrict__ par
             jt = plane * (K2 * pw) + (lb * K + la) * pw + (rem - pair * pw);
         }
     }
+    // what the tail needs from memory is asked for here, next to the partials: one round of latency, not three in a row
+    const bool lead = slice == 0 && j < hist_words && (wl & (pw - 1)) == 0;             // first lane of a pair's pw permutations
+    const size_t slot = (size_t)batch * (hist_words / pw) + (j < hist_words ? j / pw : 0);  // [batch][plane][pair]: j / pw = plane * K2 + pair
+    const int64_t sh = slice == 0 ? shift[pair] : 0;
+    const int64_t had_sum = lead ? acc_sum[slot] : 0;
+    const uint64_t had_sq = lead ? acc_sq[slot] : 0;
     unsigned long long c = 0;
     if (j < hist_words) {
+        // nblk: partials per batch (stride); nsum: how many of them hold something to add.  W loads are issued before the first is
+        // waited for (the plain loop waited for every word before it asked for the next: eight latencies in a row at 8 partials)
+        constexpr int STEP = SLICED ? 4 : 1, W = SLICED ? 4 : 8;
         const uint32_t* src = partial_all + (size_t)batch * nblk * hist_words;
-        for (int k = slice; k < nsum; k += 4) {  // nblk: partials per batch (stride); nsum: how many of them hold something to add
-            c += src[(size_t)k * hist_words + j];
-            if (sym & 4) c += src[(size_t)k * hist_words + jt];
-        }
+        auto walk = [&](int slot_j) {
+            const uint32_t* q = src + slot_j;
+            unsigned long long sum = 0;
+            for (int k = slice; k < nsum; k += W * STEP) {  // (a short last round re-reads the last partial and adds 0 for it)
+                uint32_t v[W];
+#pragma unroll
+                for (int u = 0; u < W; ++u) v[u] = q[(size_t)min(k + u * STEP, nsum - 1) * hist_words];
+#pragma unroll
+                for (int u = 0; u < W; ++u) sum += k + u * STEP < nsum ? v[u] : 0u;
+            }
+            return sum;
+        };
+        c = walk(j);
+        if (sym & 4) c += walk(jt);
     }
-    part[slice][wl] = c;
-    __syncthreads();
-    if (slice != 0 || j >= hist_words) return;
-    c = part[0][wl] + part[1][wl] + part[2][wl] + part[3][wl];
+    if constexpr (SLICED) {
+        part[slice][wl] = c;
+        __syncthreads();
+        if (slice != 0) return;
+        c = part[0][wl] + part[1][wl] + part[2][wl] + part[3][wl];
+    }
+    // every wave that is still here is WHOLE: the pw permutations of a pair are pw neighbouring lanes, summed across them below
     if (sym & 2) c >>= 1;
     const int64_t p = perm_batch0 + (int64_t)batch * B + b;
-    if (p >= perm_end || p < perm_begin) return;
-    const int64_t d = (int64_t)c - shift[pair];
-    const size_t slot = (size_t)batch * hist_words + j;
-    acc_sum[slot] += d;
-    acc_sq[slot] += (uint64_t)(d * d);
-    if (perms_out) perms_out[(size_t)(p - perm_begin) * K2 + pair] = (uint32_t)c;
+    // a permutation outside [perm_begin, perm_end) — and a lane past the last slot — contributes 0: no return in front of the shuffles
+    const bool counted = j < hist_words && p < perm_end && p >= perm_begin;
+    const int64_t d = counted ? (int64_t)c - sh : 0;
+    if (counted && perms_out) perms_out[(size_t)(p - perm_begin) * K2 + pair] = (uint32_t)c;
+    int64_t s = d;
+    uint64_t q = (uint64_t)(d * d);
+    for (int o = 1; o < pw; o <<= 1) {  // pw = 1 .. 32, a power of two: groups never straddle the wave (a wave's first j is a multiple of 64)
+        s += __shfl_xor(s, o);
+        q += __shfl_xor(q, o);
+    }
+    if (!lead) return;
+    acc_sum[slot] = had_sum + s;
+    acc_sq[slot] = had_sq + q;
 }
 
 // Reduction of the 16-bit partials (counter modes 1 and 2 of k_count / k_count_pass): per (batch, chunk) the blocks wrote
 // [16 / PW planes][cell][PW] uint16 — cells = K*K (mode 1) or K (K + 1) / 2 unordered pairs at cell = hi * (hi + 1) / 2 + lo (TRI).  ONE
 // thread owns a cell of a batch: it sums the cell's 16 permutations over the chunks (PW / 2 words per plane and chunk: 32 contiguous
 // bytes per lane at PW = 16), turns them into the counts they stand for, and adds the batch's sum of d = count - shift and of d^2
-// to ONE accumulator slot per ordered pair (acc[batch][pair]: private, no atomics, bit-reproducible) — 16 times fewer accumulator
-// bytes than k_reduce's slot per (pair, permutation), which at K = 200 were as many as the partials themselves.
+// to ONE accumulator slot per ordered pair (acc[batch][pair]: private, no atomics, bit-reproducible) — what k_reduce keeps per plane.
 // TRI: count[a][b] = count[b][a] = T{a,b} for a != b, count[a][a] = 2 T{a,a} (an edge inside a cluster is one half-list entry and
 // two entries of the full scan); `doubled` (half list with self loops: half edges weigh 2, self loops 1): count[a][b] = T{a,b} / 2,
 // count[a][a] = T{a,a} — every T{a,b}, a != b, is even by construction.
@@ -957,21 +994,22 @@ __global__ __launch_bounds__(256) void k_reduce16(const uint32_t* __restrict__ p
     }
 }
 
-// thread per slot j of a batch: sums the slot over the batches (coalesced whatever the plane width), then adds into its pair's
-// total — 16 integer atomics per pair and moment; integer addition is exact and order-independent, so the result is
-// bit-reproducible.  out_sum / out_sq are zeroed by the caller.
+// thread per slot j = plane * K2 + pair of a batch and slice of the batches (blockIdx.y: with K2 slots per plane a thread per slot
+// alone is four blocks at 30 clusters, each walking every batch): sums the slot over its batches (coalesced), then adds into its
+// pair's total — planes x slices integer atomics per pair and moment; integer addition is exact and order-independent, so the
+// result is bit-reproducible.  out_sum / out_sq are zeroed by the caller.
+constexpr int FINALIZE_SLICES = 16;
 __global__ __launch_bounds__(256) void k_finalize(const int64_t* __restrict__ acc_sum, const uint64_t* __restrict__ acc_sq, int nbatch,
-                                                  int hist_words, int pw, int K2, int64_t* __restrict__ out_sum,
-                                                  uint64_t* __restrict__ out_sq) {
+                                                  int acc_words, int K2, int64_t* __restrict__ out_sum, uint64_t* __restrict__ out_sq) {
     const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= hist_words) return;
+    if (j >= acc_words) return;
     int64_t s = 0;
     uint64_t q = 0;
-    for (int t = 0; t < nbatch; ++t) {
-        s += acc_sum[(size_t)t * hist_words + j];
-        q += acc_sq[(size_t)t * hist_words + j];
+    for (int t = blockIdx.y; t < nbatch; t += gridDim.y) {
+        s += acc_sum[(size_t)t * acc_words + j];
+        q += acc_sq[(size_t)t * acc_words + j];
     }
-    const int pair = (j % (K2 * pw)) / pw;
+    const int pair = j % K2;
     atomicAdd(reinterpret_cast<unsigned long long*>(out_sum) + pair, (unsigned long long)s);
     atomicAdd(reinterpret_cast<unsigned long long*>(out_sq) + pair, (unsigned long long)q);
 }
@@ -1191,6 +1229,7 @@ struct sqgr_nhood {
     DevBuf<uint8_t> slab;    // 2 buffers
     hipEvent_t ev_shuffled[2] = {nullptr, nullptr}, ev_counted[2] = {nullptr, nullptr};
     ~sqgr_nhood() {
+        if (fin_host) (void)hipHostFree(fin_host);
         for (int i = 0; i < 2; ++i) {
             if (ev_shuffled[i]) (void)hipEventDestroy(ev_shuffled[i]);
             if (ev_counted[i]) (void)hipEventDestroy(ev_counted[i]);
@@ -1203,9 +1242,11 @@ struct sqgr_nhood {
     // have to BE labels: the next batch's rows, or zeros behind the last batch of the launch, see count_batches)
     size_t slab_stride() const { return (size_t)nbatch * n * B * (wide() ? 2 : 1) + SEG_SLAB_PAD; }
     DevBuf<uint32_t> partial;
-    DevBuf<int64_t> acc_sum;
-    DevBuf<uint64_t> acc_sq;
-    DevBuf<int64_t> shift, fin;  // fin: [K2] sum of d, then [K2] sum of d*d (uint64 bit patterns) — one all-reduce
+    // ONE block [sum of d per slot | sum of d*d per slot | fin], cleared by one fill per run (begin_run) where three allocations took
+    // three.  fin: [K2] sum of d, then [K2] sum of d*d (uint64 bit patterns) — one all-reduce
+    DevBuf<int64_t> acc;
+    DevBuf<int64_t> shift;
+    int64_t* fin_host = nullptr;  // pinned twin of fin (ensure_workspace): the moments leave in ONE copy, split on the host (finish_run)
     sqgr_comm* comm = nullptr;   // optional: moments are all-reduced on the device (sqgr_nhood_set_comm)
     DevBuf<uint32_t> perms_dev;
     DevBuf<uint8_t> stage;
@@ -1251,9 +1292,13 @@ struct sqgr_nhood {
     int plane_w() const { return (B == 16 && !wide() && be() > 0) ? be() : 16; }
     // 32-bit words of ONE block-partial set of a batch's chunk: K*K*B counters, or (16-bit modes) cells x 16 half words
     size_t part_words() const { return cm() ? (size_t)cells() * 8 : (size_t)hist_words(); }
-    // accumulator slots of a batch and their plane width (k_finalize): one per (pair, permutation) — or, 16-bit modes, one per pair
-    int acc_words() const { return cm() ? K2 : hist_words(); }
-    int acc_pw() const { return cm() ? 1 : partial_w(); }
+    // accumulator slots of a batch, [plane][pair] (k_finalize): one per pair and plane of the partials (k_reduce) — 16-bit modes: one per pair
+    int acc_words() const { return cm() ? K2 : K2 * (B / partial_w()); }
+    size_t acc_slots() const { return (size_t)nbatch * acc_words(); }
+    size_t acc_total() const { return 2 * acc_slots() + (size_t)2 * K2; }
+    int64_t* acc_sum() const { return acc.p; }
+    uint64_t* acc_sq() const { return reinterpret_cast<uint64_t*>(acc.p + acc_slots()); }
+    int64_t* fin() const { return acc.p + 2 * acc_slots(); }
     // 16-bit counters: the most edges one block may count — no counter can pass 65 535 whatever the labels are (a block's cell
     // receives at most weight x edges; weight 2 on half lists with self loops) — in whole iterations of the kernel that runs
     uint32_t edge_step() const { return be() == 16 ? 1024u : (be() == 8 ? 2048u : 4096u); }
@@ -1398,10 +1443,9 @@ int sqgr_nhood::ensure_workspace() {
         if (!ev_counted[i]) SQGR_HIP(hipEventCreateWithFlags(&ev_counted[i], hipEventDisableTiming));
     }
     SQGR_TRY(partial.ensure(partial_words()));
-    SQGR_TRY(acc_sum.ensure((size_t)nbatch * acc_words()));
-    SQGR_TRY(acc_sq.ensure((size_t)nbatch * acc_words()));
+    SQGR_TRY(acc.ensure(acc_total()));
     SQGR_TRY(shift.ensure((size_t)K2));
-    SQGR_TRY(fin.ensure((size_t)2 * K2));
+    if (!fin_host) SQGR_HIP(hipHostMalloc(reinterpret_cast<void**>(&fin_host), (size_t)2 * K2 * 8, hipHostMallocDefault));  // (K2 is the plan's for good)
     return SQGR_OK;
 }
 
@@ -1411,8 +1455,7 @@ int sqgr_nhood::begin_run(const int64_t* shift_host) {
         SQGR_HIP(hipMemcpyAsync(shift.p, shift_host, (size_t)K2 * 8, hipMemcpyHostToDevice, st));
     else
         SQGR_HIP(hipMemsetAsync(shift.p, 0, (size_t)K2 * 8, st));
-    SQGR_HIP(hipMemsetAsync(acc_sum.p, 0, (size_t)nbatch * acc_words() * 8, st));
-    SQGR_HIP(hipMemsetAsync(acc_sq.p, 0, (size_t)nbatch * acc_words() * 8, st));
+    SQGR_HIP(hipMemsetAsync(acc.p, 0, acc_total() * 8, st));  // the slots and fin (k_finalize adds into it)
     return SQGR_OK;
 }
 
@@ -1423,9 +1466,8 @@ int sqgr_nhood::finish_run(int local_rc, int64_t n_perms, int64_t* out_sum, uint
     auto finalize = [&]() -> int {
         const int hw = acc_words();
         LaunchTimer t(ctx, "nhood_finalize");
-        SQGR_HIP(hipMemsetAsync(fin.p, 0, (size_t)2 * K2 * 8, st));
-        k_finalize<<<(unsigned)ceil_div(hw, 256), 256, 0, st>>>(acc_sum.p, acc_sq.p, nbatch, hw, acc_pw(), K2, fin.p,
-                                                               reinterpret_cast<uint64_t*>(fin.p + K2));
+        const dim3 grid((unsigned)ceil_div(hw, 256), (unsigned)std::min(nbatch, FINALIZE_SLICES));
+        k_finalize<<<grid, 256, 0, st>>>(acc_sum(), acc_sq(), nbatch, hw, K2, fin(), reinterpret_cast<uint64_t*>(fin() + K2));  // fin: zero since begin_run
         SQGR_HIP(hipGetLastError());
         return SQGR_OK;
     };
@@ -1438,12 +1480,15 @@ int sqgr_nhood::finish_run(int local_rc, int64_t n_perms, int64_t* out_sum, uint
     SQGR_TRY(comm_agree(comm, local_rc, st));
     // multi-GPU: the ranks ran disjoint permutation ranges; one RCCL all-reduce of the 2*K*K exact integer moments on the
     // device, then every rank copies out the global sums
-    SQGR_TRY(comm_allreduce_i64_dev(comm, fin.p, (size_t)2 * K2, false, st));
-    SQGR_HIP(hipMemcpyAsync(out_sum, fin.p, (size_t)K2 * 8, hipMemcpyDeviceToHost, st));
-    SQGR_HIP(hipMemcpyAsync(out_sumsq, fin.p + K2, (size_t)K2 * 8, hipMemcpyDeviceToHost, st));
+    SQGR_TRY(comm_allreduce_i64_dev(comm, fin(), (size_t)2 * K2, false, st));
+    // both halves of fin in one copy into the plan's pinned block (two pageable copies of K2 * 8 bytes each staged and waited
+    // on their own in front of the synchronisation), split for the caller behind it
+    SQGR_HIP(hipMemcpyAsync(fin_host, fin(), (size_t)2 * K2 * 8, hipMemcpyDeviceToHost, st));
     if (out_perms && n_perms > 0)
         SQGR_HIP(hipMemcpyAsync(out_perms, perms_dev.p, (size_t)n_perms * K2 * 4, hipMemcpyDeviceToHost, st));
     SQGR_HIP(hipStreamSynchronize(st));
+    memcpy(out_sum, fin_host, (size_t)K2 * 8);
+    memcpy(out_sumsq, fin_host + K2, (size_t)K2 * 8);
     return SQGR_OK;
 }
 
@@ -1661,8 +1706,8 @@ int sqgr_nhood::reduce_batches(int nb, int64_t perm_batch0, int64_t perm_begin, 
         const dim3 grid((unsigned)ceil_div(ncell, 256), nb);
         const int dbl = (sym_launch & 2) ? 1 : 0;
 #define SQGR_RED16(TRI, PW)                                                                                                                    \
-    k_reduce16<TRI, PW><<<grid, 256, 0, ctx->stream>>>(partial.p, nblk_launch, ncell, K, dbl, shift.p, perm_batch0, perm_begin, perm_end, acc_sum.p, \
-                                                       acc_sq.p, perms_out_dev)
+    k_reduce16<TRI, PW><<<grid, 256, 0, ctx->stream>>>(partial.p, nblk_launch, ncell, K, dbl, shift.p, perm_batch0, perm_begin, perm_end, acc_sum(), \
+                                                       acc_sq(), perms_out_dev)
 #define SQGR_RED16_W(TRI)                                \
     switch (pw) {                                        \
         case 16: SQGR_RED16(TRI, 16); break;             \
@@ -1681,9 +1726,14 @@ int sqgr_nhood::reduce_batches(int nb, int64_t perm_batch0, int64_t perm_begin, 
         k_sum_chunks<<<dim3((unsigned)ceil_div(hw, 256), nb), 256, 0, ctx->stream>>>(partial.p, nblk_launch, hw);
         nsum = 1;
     }
-    k_reduce<<<dim3((unsigned)ceil_div(hw, 64), nb), 256, 0, ctx->stream>>>(partial.p, nblk_launch, nsum, hw, B, partial_w(), K, sym_launch, shift.p,
-                                                                            perm_batch0, perm_begin, perm_end, acc_sum.p,
-                                                                            acc_sq.p, perms_out_dev);
+    if (nsum >= REDUCE_SLICED_FROM)
+        k_reduce<true><<<dim3((unsigned)ceil_div(hw, 64), nb), 256, 0, ctx->stream>>>(partial.p, nblk_launch, nsum, hw, B, partial_w(), K, sym_launch,
+                                                                                      shift.p, perm_batch0, perm_begin, perm_end, acc_sum(),
+                                                                                      acc_sq(), perms_out_dev);
+    else
+        k_reduce<false><<<dim3((unsigned)ceil_div(hw, 256), nb), 256, 0, ctx->stream>>>(partial.p, nblk_launch, nsum, hw, B, partial_w(), K, sym_launch,
+                                                                                        shift.p, perm_batch0, perm_begin, perm_end, acc_sum(),
+                                                                                        acc_sq(), perms_out_dev);
     SQGR_HIP(hipGetLastError());
     return SQGR_OK;
 }
@@ -1816,7 +1866,7 @@ int sqgr_nhood_tune(sqgr_nhood* plan, int32_t perms_per_pass, int32_t blocks_per
     plan->nblk = blocks_per_batch;
     plan->nbatch = batches_per_launch;  // 0: automatic (resolve_tuning)
     // force re-allocation with the new geometry
-    plan->keys.release(); plan->slab.release(); plan->partial.release(); plan->acc_sum.release(); plan->acc_sq.release();
+    plan->keys.release(); plan->slab.release(); plan->partial.release(); plan->acc.release();
     return SQGR_OK;
 }
 
@@ -1910,14 +1960,13 @@ int sqgr_nhood_counts_batch(sqgr_ctx* ctx, const sqgr_graph* g, const uint8_t* l
     int rc = SQGR_OK;
     do {
         if ((rc = p->ensure_workspace()) != SQGR_OK) break;
-        const int B = p->B, K2 = p->K2, hw = p->acc_words();
+        const int B = p->B, K2 = p->K2;
         const int64_t per_launch = (int64_t)p->nbatch * B;
         hipStream_t st = ctx->stream;
         if ((rc = p->stage.ensure((size_t)per_launch * n)) != SQGR_OK) break;
         if ((rc = p->perms_dev.ensure((size_t)(n_perms > 0 ? n_perms : 1) * K2)) != SQGR_OK) break;
         hipError_t e = hipMemsetAsync(p->shift.p, 0, (size_t)K2 * 8, st);
-        if (e == hipSuccess) e = hipMemsetAsync(p->acc_sum.p, 0, (size_t)p->nbatch * hw * 8, st);
-        if (e == hipSuccess) e = hipMemsetAsync(p->acc_sq.p, 0, (size_t)p->nbatch * hw * 8, st);
+        if (e == hipSuccess) e = hipMemsetAsync(p->acc.p, 0, p->acc_total() * 8, st);
         for (int64_t p0 = 0; p0 < n_perms && e == hipSuccess && rc == SQGR_OK; p0 += per_launch) {
             const int64_t todo = (n_perms - p0 < per_launch) ? n_perms - p0 : per_launch;
             const int nb = (int)ceil_div(todo, B);
