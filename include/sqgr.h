@@ -416,6 +416,10 @@ int sqgr_sepal_destroy(sqgr_sepal* h);
 int sqgr_graph_triangles(sqgr_ctx* ctx, const sqgr_graph* g, int64_t* out_two_tri);
 int sqgr_group_bfs(sqgr_ctx* ctx, const sqgr_graph* g, const int32_t* labels, int32_t K, int64_t* out_adjacent, int64_t* out_dist_sum,
                    int64_t* out_reached, int64_t* out_levels);
+/* sqgr_group_bfs_hook (parity hook): the same with the grid of the level kernel given: grid_blocks >= 1 replaces 8 x compute units as the
+ * cap on its blocks (a block then strides over the nodes in more trips), 0 = the default.  The integers do not depend on it. */
+int sqgr_group_bfs_hook(sqgr_ctx* ctx, const sqgr_graph* g, const int32_t* labels, int32_t K, int64_t* out_adjacent, int64_t* out_dist_sum,
+                        int64_t* out_reached, int64_t* out_levels, int32_t grid_blocks);
 
 /* ---- calculate_niche_cellcharter: a full-covariance Gaussian mixture fitted by EM in float64 -----------------------------------
  * Replaces `GaussianMixture(n_components, random_state, init_params="random_from_data").fit(embedding).predict(embedding)`
@@ -433,6 +437,14 @@ int sqgr_group_bfs(sqgr_ctx* ctx, const sqgr_graph* g, const int32_t* labels, in
 int sqgr_gmm_fit(sqgr_ctx* ctx, const double* X, int64_t n, int32_t d, int32_t k, const int64_t* init_rows, double reg_covar, double tol,
                  int32_t max_iter, double* out_weights, double* out_means, double* out_covariances, double* out_lower_bounds,
                  int32_t* out_n_iter, int32_t* out_converged, int32_t* out_labels);
+/* sqgr_gmm_geometry: the launch geometry sqgr_gmm_fit derives from (n, d, k), from the function the fit itself calls.  Needs no device.
+ *   out int64[20] = {columns of P padded to a strip, E-step tiles per block, E-step blocks, rows of a chunk of the covariance sums, rows
+ *   of a chunk of the weighted sums, covariance chunks, weighted-sum chunks, rows staged at a time by the weighted sums, the same by
+ *   the covariance sums, LDS bytes of the E-step, of the weighted sums, of the covariance sums; then the constants these are formed
+ *   from: rows of an E-step tile, most E-step blocks, most chunks x components of the covariance grid, fewest rows of a chunk, most
+ *   chunks of the weighted sums, columns of a strip of P, bytes of a stage, bytes of the group reduction}.
+ *   SQGR_ERR_INVALID outside 1 <= d, k <= 64, 1 <= n < 2^31. */
+int sqgr_gmm_geometry(int64_t n, int32_t d, int32_t k, int64_t* out);
 
 /* ---- niche feature matrices: stage 1 of the three niche flavours, everything in front of scanpy (gr/_niche.py) -------------------
  * Float64 throughout; every sum over a row's stored entries runs in ascending column order with separately rounded products and
@@ -506,6 +518,11 @@ int sqgr_pca_fill_aggregate(sqgr_pca* h, int32_t col0, const sqgr_graph* g, cons
 int sqgr_pca_moments(sqgr_pca* h, double* out_mean, double* out_scatter);
 int sqgr_pca_project(sqgr_pca* h, const double* components, int32_t c, double* out);
 int sqgr_pca_destroy(sqgr_pca* h);
+/* sqgr_pca_geometry: the launch geometry sqgr_pca_moments derives from (n, D), from the function it calls itself.  Needs no device.
+ *   out int64[10] = {column tiles, tile pairs of the upper triangle, rows of a chunk of the column sums, rows of a chunk of the scatter,
+ *   chunks of the column sums, chunks of the scatter; then the constants these are formed from: the chunk unit, most chunks, the target
+ *   of tile pairs x chunks, columns of a tile}.  SQGR_ERR_INVALID outside 2 <= n < 2^31, 2 <= D <= 4096. */
+int sqgr_pca_geometry(int64_t n, int32_t D, int64_t* out);
 
 /* ---- exact kNN in feature space and UMAP's fuzzy kNN weights: the parts of `sc.pp.neighbors(adata, n_neighbors, use_rep="X")` that
  * grow with n (gr/_niche.py:1417, in front of `sc.tl.leiden`).  Float64 throughout, no float atomics, no FMA.
@@ -569,6 +586,10 @@ int sqgr_fuzzy_knn(sqgr_ctx* ctx, const double* dist, int64_t n, int32_t k, doub
 int sqgr_leiden_info(int64_t* out_info);
 int sqgr_leiden(sqgr_ctx* ctx, int64_t n, const int64_t* indptr, const int32_t* indices, const int32_t* weights, double resolution,
                 int32_t n_iterations, int32_t* out_labels, int64_t* out_stats);
+/* sqgr_leiden_hook (parity hook): the same with the grid of the grid-stride kernels given: grid_blocks >= 1 replaces 8 x compute units
+ * (the kernels then cover the rows and entries in more trips), 0 = the default.  Labels and stats do not depend on it. */
+int sqgr_leiden_hook(sqgr_ctx* ctx, int64_t n, const int64_t* indptr, const int32_t* indices, const int32_t* weights, double resolution,
+                     int32_t n_iterations, int32_t* out_labels, int64_t* out_stats, int32_t grid_blocks);
 
 /* ---- Multiplex Leiden on two layers over the same vertices: what `calculate_niche_spatialleiden` (gr/_niche.py:466-620) gets from
  * spatialleiden, i.e. leidenalg's optimise_partition_multiplex over one RBConfigurationVertexPartition per layer with layer_weights
@@ -609,6 +630,10 @@ int sqgr_leiden_multiplex_info(int64_t* out_info);
 int sqgr_leiden_multiplex(sqgr_ctx* ctx, int64_t n, const int64_t* indptr0, const int32_t* indices0, const int32_t* weights0,
                           const int64_t* indptr1, const int32_t* indices1, const int32_t* weights1, double resolution0, double resolution1,
                           double layer_ratio, int32_t n_iterations, int32_t* out_labels, int64_t* out_stats);
+/* sqgr_leiden_multiplex_hook (parity hook): grid_blocks as for sqgr_leiden_hook. */
+int sqgr_leiden_multiplex_hook(sqgr_ctx* ctx, int64_t n, const int64_t* indptr0, const int32_t* indices0, const int32_t* weights0,
+                               const int64_t* indptr1, const int32_t* indices1, const int32_t* weights1, double resolution0, double resolution1,
+                               double layer_ratio, int32_t n_iterations, int32_t* out_labels, int64_t* out_stats, int32_t grid_blocks);
 
 /* ---- mask_graph: `LineString([a_k, b_k]).within(polygon_mask)` for every edge of a spatial graph (gr/_build.py:852-954), as the numpy
  * restatement squidpy_amd/gr/_mask.py evaluates it: plain float64 cross products, divisions and comparisons, every operation rounded

@@ -107,6 +107,8 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     ),
     "sqgr_graph_triangles": (C.c_int, [C.c_void_p, C.c_void_p, c_i64p]),
     "sqgr_group_bfs": (C.c_int, [C.c_void_p, C.c_void_p, c_i32p, C.c_int32, c_i64p, c_i64p, c_i64p, c_i64p]),
+    "sqgr_group_bfs_hook": (C.c_int, [C.c_void_p, C.c_void_p, c_i32p, C.c_int32, c_i64p, c_i64p, c_i64p, c_i64p, C.c_int32]),
+    "sqgr_gmm_geometry": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, c_i64p]),
     "sqgr_gmm_fit": (
         C.c_int,
         [C.c_void_p, c_f64p, C.c_int64, C.c_int32, C.c_int32, c_i64p, C.c_double, C.c_double, C.c_int32, c_f64p, c_f64p, c_f64p, c_f64p,
@@ -120,6 +122,7 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "sqgr_niche_aggregate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, c_f64p, C.c_int64]),
     "sqgr_niche_label_hops": (C.c_int, [C.c_void_p, C.c_void_p, c_i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_f64p]),
     "sqgr_pca_info": (C.c_int, [c_i64p]),
+    "sqgr_pca_geometry": (C.c_int, [C.c_int64, C.c_int32, c_i64p]),
     "sqgr_pca_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]),
     "sqgr_pca_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
     "sqgr_pca_fill_aggregate": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
@@ -131,7 +134,10 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "sqgr_fuzzy_knn": (C.c_int, [C.c_void_p, c_f64p, C.c_int64, C.c_int32, C.c_double, c_f64p, c_f64p, c_i32p, c_f64p]),
     "sqgr_leiden_info": (C.c_int, [c_i64p]),
     "sqgr_leiden": (C.c_int, [C.c_void_p, C.c_int64, c_i64p, c_i32p, c_i32p, C.c_double, C.c_int32, c_i32p, c_i64p]),
+    "sqgr_leiden_hook": (C.c_int, [C.c_void_p, C.c_int64, c_i64p, c_i32p, c_i32p, C.c_double, C.c_int32, c_i32p, c_i64p, C.c_int32]),
     "sqgr_leiden_multiplex_info": (C.c_int, [c_i64p]),
+    "sqgr_leiden_multiplex_hook": (C.c_int, [C.c_void_p, C.c_int64, c_i64p, c_i32p, c_i32p, c_i64p, c_i32p, c_i32p, C.c_double, C.c_double,
+                                             C.c_double, C.c_int32, c_i32p, c_i64p, C.c_int32]),
     "sqgr_leiden_multiplex": (C.c_int, [C.c_void_p, C.c_int64, c_i64p, c_i32p, c_i32p, c_i64p, c_i32p, c_i32p, C.c_double, C.c_double, C.c_double,
                                         C.c_int32, c_i32p, c_i64p]),
     "sqgr_mask_info": (C.c_int, [c_i64p]),
@@ -526,17 +532,36 @@ def graph_triangles(ctx: Context, g: Graph) -> np.ndarray:
     return out
 
 
-def group_bfs(ctx: Context, g: Graph, labels: np.ndarray, n_cls: int) -> tuple[np.ndarray, np.ndarray, np.ndarray, int]:
+def group_bfs(ctx: Context, g: Graph, labels: np.ndarray, n_cls: int, grid_blocks: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray, int]:
     """One multi-source BFS per group of an undirected simple graph (``sqgr_group_bfs``); ``labels`` in ``[-1, n_cls)``, -1 = no group.
-    Returns ``(adjacent, dist_sum, reached)`` — int64[n_cls] each — and the largest finite distance of the call."""
+    Returns ``(adjacent, dist_sum, reached)`` — int64[n_cls] each — and the largest finite distance of the call.  ``grid_blocks`` (0:
+    the library's) goes through the parity hook."""
     labels = _as(labels, np.int32)
     if len(labels) != g.n:
         raise ValueError(f"Expected {g.n} labels, found {len(labels)}.")
     adjacent, dist_sum, reached = (np.zeros(n_cls, dtype=np.int64) for _ in range(3))
     levels = np.zeros(1, dtype=np.int64)
-    _check(ctx.lib, ctx.lib.sqgr_group_bfs(ctx.h, g.h, _ptr(labels, c_i32p), int(n_cls), _ptr(adjacent, c_i64p), _ptr(dist_sum, c_i64p),
-                                           _ptr(reached, c_i64p), _ptr(levels, c_i64p)))
+    args = (ctx.h, g.h, _ptr(labels, c_i32p), int(n_cls), _ptr(adjacent, c_i64p), _ptr(dist_sum, c_i64p), _ptr(reached, c_i64p),
+            _ptr(levels, c_i64p))
+    if grid_blocks:
+        _check(ctx.lib, ctx.lib.sqgr_group_bfs_hook(*args, int(grid_blocks)))
+    else:
+        _check(ctx.lib, ctx.lib.sqgr_group_bfs(*args))
     return adjacent, dist_sum, reached, int(levels[0])
+
+
+GMM_GEOMETRY = ("dp", "e_tiles_per_block", "e_blocks", "rows_per_chunk", "sums_rows_per_chunk", "nchunks", "sums_nchunks", "rt_sums", "rt_cov",
+                "lds_e", "lds_sums", "lds_cov", "E_T", "E_MAX_BLOCKS", "M_MAX_BLOCKS", "M_MIN_ROWS", "M_SUMS_BLOCKS", "E_JT", "M_STAGE_BYTES",
+                "M_RED_BYTES")
+
+
+def gmm_geometry(n: int, d: int, k: int) -> dict[str, int]:
+    """The launch geometry ``gmm_fit`` derives from ``(n, d, k)`` and the constants it is formed from (``sqgr_gmm_geometry``); needs the
+    library, not a device."""
+    lib = load_library()
+    out = np.zeros(len(GMM_GEOMETRY), dtype=np.int64)
+    _check(lib, lib.sqgr_gmm_geometry(int(n), int(d), int(k), _ptr(out, c_i64p)))
+    return dict(zip(GMM_GEOMETRY, (int(v) for v in out)))
 
 
 def gmm_fit(
@@ -939,6 +964,19 @@ def pca_info() -> dict[str, int]:
     return {"chunk_rows": int(out[0]), "max_features": int(out[1]), "max_components": int(out[2]), "tile_columns": int(out[3])}
 
 
+PCA_GEOMETRY = ("nt", "npairs", "mean_rows", "scat_rows", "mean_chunks", "scat_chunks", "PCA_CHUNK", "PCA_MAX_CHUNKS", "PCA_TARGET_BLOCKS",
+                "PCA_TILE")
+
+
+def pca_geometry(n: int, d: int) -> dict[str, int]:
+    """The launch geometry ``DevicePCA.moments`` derives from ``(n, D)`` and the constants it is formed from (``sqgr_pca_geometry``);
+    needs the library, not a device."""
+    lib = load_library()
+    out = np.zeros(len(PCA_GEOMETRY), dtype=np.int64)
+    _check(lib, lib.sqgr_pca_geometry(int(n), int(d), _ptr(out, c_i64p)))
+    return dict(zip(PCA_GEOMETRY, (int(v) for v in out)))
+
+
 class DevicePCA:
     """A dense float64 matrix ``F[n][D]`` resident on the device and the parts of a PCA that grow with ``n`` (``sqgr_pca``): its
     column means and centred scatter matrix, and the projection on components the caller found from them."""
@@ -1036,9 +1074,9 @@ def leiden_info() -> dict[str, int]:
 
 
 def leiden(ctx: Context, indptr: np.ndarray, indices: np.ndarray, weights: np.ndarray, resolution: float,
-           n_iterations: int = -1) -> tuple[np.ndarray, dict[str, int]]:
+           n_iterations: int = -1, grid_blocks: int = 0) -> tuple[np.ndarray, dict[str, int]]:
     """``sqgr_leiden``: ``(labels int32 (n,), stats)`` of a canonical symmetric CSR graph with int32 weights >= 1; ``stats`` has the
-    keys of ``LEIDEN_STATS``."""
+    keys of ``LEIDEN_STATS``.  ``grid_blocks`` (0: the library's) goes through the parity hook."""
     indptr = _as(indptr, np.int64)
     indices = _as(indices, np.int32)
     weights = _as(weights, np.int32)
@@ -1047,8 +1085,12 @@ def leiden(ctx: Context, indptr: np.ndarray, indices: np.ndarray, weights: np.nd
     assert indptr[-1] == indices.shape[0], (indptr[-1], indices.shape)
     labels = np.empty(n, dtype=np.int32)
     stats = np.zeros(len(LEIDEN_STATS), dtype=np.int64)
-    _check(ctx.lib, ctx.lib.sqgr_leiden(ctx.h, n, _ptr(indptr, c_i64p), _ptr(indices, c_i32p), _ptr(weights, c_i32p), float(resolution),
-                                        int(n_iterations), _ptr(labels, c_i32p), _ptr(stats, c_i64p)))
+    args = (ctx.h, n, _ptr(indptr, c_i64p), _ptr(indices, c_i32p), _ptr(weights, c_i32p), float(resolution), int(n_iterations),
+            _ptr(labels, c_i32p), _ptr(stats, c_i64p))
+    if grid_blocks:
+        _check(ctx.lib, ctx.lib.sqgr_leiden_hook(*args, int(grid_blocks)))
+    else:
+        _check(ctx.lib, ctx.lib.sqgr_leiden(*args))
     return labels, dict(zip(LEIDEN_STATS, (int(s) for s in stats)))
 
 
@@ -1065,9 +1107,10 @@ def leiden_multiplex_info() -> dict[str, int]:
 
 
 def leiden_multiplex(ctx: Context, layer0: tuple, layer1: tuple, resolutions: tuple[float, float] = (1.0, 1.0), layer_ratio: float = 1.0,
-                     n_iterations: int = -1) -> tuple[np.ndarray, dict[str, int]]:
+                     n_iterations: int = -1, grid_blocks: int = 0) -> tuple[np.ndarray, dict[str, int]]:
     """``sqgr_leiden_multiplex``: ``(labels int32 (n,), stats)`` of two ``(indptr, indices, weights)`` layers over the same vertices,
-    each a canonical symmetric CSR graph with int32 weights >= 1 (a layer may be empty); ``stats`` has the keys of ``MULTIPLEX_STATS``."""
+    each a canonical symmetric CSR graph with int32 weights >= 1 (a layer may be empty); ``stats`` has the keys of ``MULTIPLEX_STATS``.
+    ``grid_blocks`` (0: the library's) goes through the parity hook."""
     args = []
     n = np.asarray(layer0[0]).shape[0] - 1
     for indptr, indices, weights in (layer0, layer1):
@@ -1078,8 +1121,11 @@ def leiden_multiplex(ctx: Context, layer0: tuple, layer1: tuple, resolutions: tu
     labels = np.empty(n, dtype=np.int32)
     stats = np.zeros(len(MULTIPLEX_STATS), dtype=np.int64)
     ptrs = [_ptr(a, c_i64p if i % 3 == 0 else c_i32p) for i, a in enumerate(args)]
-    _check(ctx.lib, ctx.lib.sqgr_leiden_multiplex(ctx.h, n, *ptrs, float(resolutions[0]), float(resolutions[1]), float(layer_ratio),
-                                                  int(n_iterations), _ptr(labels, c_i32p), _ptr(stats, c_i64p)))
+    tail = (float(resolutions[0]), float(resolutions[1]), float(layer_ratio), int(n_iterations), _ptr(labels, c_i32p), _ptr(stats, c_i64p))
+    if grid_blocks:
+        _check(ctx.lib, ctx.lib.sqgr_leiden_multiplex_hook(ctx.h, n, *ptrs, *tail, int(grid_blocks)))
+    else:
+        _check(ctx.lib, ctx.lib.sqgr_leiden_multiplex(ctx.h, n, *ptrs, *tail))
     return labels, dict(zip(MULTIPLEX_STATS, (int(s) for s in stats)))
 
 

@@ -212,7 +212,13 @@ int sqgr_graph_triangles(sqgr_ctx* ctx, const sqgr_graph* g, int64_t* out_two_tr
 
 int sqgr_group_bfs(sqgr_ctx* ctx, const sqgr_graph* g, const int32_t* labels, int32_t K, int64_t* out_adjacent, int64_t* out_dist_sum,
                    int64_t* out_reached, int64_t* out_levels) {
+    return sqgr_group_bfs_hook(ctx, g, labels, K, out_adjacent, out_dist_sum, out_reached, out_levels, 0);
+}
+
+int sqgr_group_bfs_hook(sqgr_ctx* ctx, const sqgr_graph* g, const int32_t* labels, int32_t K, int64_t* out_adjacent, int64_t* out_dist_sum,
+                        int64_t* out_reached, int64_t* out_levels, int32_t grid_blocks) {
     SQGR_REQUIRE(ctx && g && labels && out_adjacent && out_dist_sum && out_reached && out_levels, "null argument");
+    SQGR_REQUIRE(grid_blocks >= 0, "grid_blocks=%d", grid_blocks);
     SQGR_REQUIRE(g->ctx == ctx, "graph belongs to a different context");
     SQGR_REQUIRE(K >= 1, "K=%d", K);
     const int64_t n = g->n;
@@ -231,7 +237,7 @@ int sqgr_group_bfs(sqgr_ctx* ctx, const sqgr_graph* g, const int32_t* labels, in
     SQGR_HIP(hipMemsetAsync(counts.p, 0, ((size_t)K * 3 + 2) * 8, st));
     unsigned long long* state = counts.p + (size_t)K * 3;
     const unsigned node_blocks = (unsigned)ceil_div(n, CENT_T);
-    const unsigned grid = std::min<unsigned>(node_blocks, 8u * (unsigned)std::max(ctx->cu_count, 1));
+    const unsigned grid = std::min<unsigned>(node_blocks, grid_blocks ? (unsigned)grid_blocks : 8u * (unsigned)std::max(ctx->cu_count, 1));
     for (int32_t base = 0; base < K; base += 64) {
         const int kp = std::min(64, K - base);
         const uint64_t full = kp == 64 ? ~(uint64_t)0 : (((uint64_t)1 << kp) - 1);

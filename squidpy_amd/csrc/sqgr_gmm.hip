@@ -457,6 +457,18 @@ GmmGeometry gmm_geometry(int64_t n, int d, int k) {
 
 using namespace sqgr;
 
+int sqgr_gmm_geometry(int64_t n, int32_t d, int32_t k, int64_t* out) {
+    SQGR_REQUIRE(out, "null argument");
+    SQGR_REQUIRE(n >= 1 && d >= 1 && d <= GMM_MAX && k >= 1 && k <= GMM_MAX && n <= (int64_t)INT32_MAX, "sqgr_gmm_geometry: n=%lld d=%d k=%d",
+                 (long long)n, d, k);
+    const GmmGeometry q = gmm_geometry(n, d, k);
+    const int64_t v[20] = {q.dp, q.e_tiles_per_block, q.e_blocks, q.rows_per_chunk, q.sums_rows_per_chunk, q.nchunks, q.sums_nchunks, q.rt_sums,
+                           q.rt_cov, (int64_t)q.lds_e, (int64_t)q.lds_sums, (int64_t)q.lds_cov, E_T, E_MAX_BLOCKS, M_MAX_BLOCKS, M_MIN_ROWS,
+                           M_SUMS_BLOCKS, E_JT, (int64_t)M_STAGE_BYTES, (int64_t)M_T * M_RED * 8};
+    std::copy(v, v + 20, out);
+    return SQGR_OK;
+}
+
 int sqgr_gmm_fit(sqgr_ctx* ctx, const double* X, int64_t n, int32_t d, int32_t k, const int64_t* init_rows, double reg_covar, double tol,
                  int32_t max_iter, double* out_weights, double* out_means, double* out_covariances, double* out_lower_bounds,
                  int32_t* out_n_iter, int32_t* out_converged, int32_t* out_labels) {

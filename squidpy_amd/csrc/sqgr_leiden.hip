@@ -283,5 +283,10 @@ int sqgr_leiden_info(int64_t* out_info) {
 
 int sqgr_leiden(sqgr_ctx* ctx, int64_t n, const int64_t* indptr, const int32_t* indices, const int32_t* weights, double resolution,
                 int32_t n_iterations, int32_t* out_labels, int64_t* out_stats) {
-    return leiden_run<1, OneLayer>(ctx, n, &indptr, &indices, &weights, &resolution, 1.0, n_iterations, out_labels, out_stats);
+    return sqgr_leiden_hook(ctx, n, indptr, indices, weights, resolution, n_iterations, out_labels, out_stats, 0);
+}
+
+int sqgr_leiden_hook(sqgr_ctx* ctx, int64_t n, const int64_t* indptr, const int32_t* indices, const int32_t* weights, double resolution,
+                     int32_t n_iterations, int32_t* out_labels, int64_t* out_stats, int32_t grid_blocks) {
+    return leiden_run<1, OneLayer>(ctx, n, &indptr, &indices, &weights, &resolution, 1.0, n_iterations, out_labels, out_stats, grid_blocks);
 }

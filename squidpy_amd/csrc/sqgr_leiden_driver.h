@@ -296,10 +296,12 @@ struct LeidenDriver {
     }
 };
 
-// the entry point: NL layers over the same n vertices, one resolution per layer; layer_ratio is read where NL > 1
+// the entry point: NL layers over the same n vertices, one resolution per layer; layer_ratio is read where NL > 1;
+// grid_blocks >= 1 replaces the default grid of the grid-stride kernels (the *_hook entry points, tests)
 template <int NL, class F>
 int leiden_run(sqgr_ctx* ctx, int64_t n, const int64_t* const* indptr, const int32_t* const* indices, const int32_t* const* weights,
-               const double* resolution, double layer_ratio, int32_t n_iterations, int32_t* out_labels, int64_t* out_stats) {
+               const double* resolution, double layer_ratio, int32_t n_iterations, int32_t* out_labels, int64_t* out_stats, int32_t grid_blocks) {
+    SQGR_REQUIRE(grid_blocks >= 0, "%s: grid_blocks=%d", F::NAME, grid_blocks);
     SQGR_REQUIRE(ctx && out_labels && out_stats && std::all_of(indptr, indptr + NL, [](const int64_t* p) { return p; }), "null argument");
     SQGR_REQUIRE(n >= 1, "%s: n=%lld", F::NAME, (long long)n);
     for (int l = 0; l < NL; ++l)
@@ -335,7 +337,7 @@ int leiden_run(sqgr_ctx* ctx, int64_t n, const int64_t* const* indptr, const int
     LeidenDriver<NL, F> S;
     S.ctx = ctx;
     S.st = ctx->stream;
-    S.grid = 8u * (unsigned)std::max(ctx->cu_count, 1);
+    S.grid = grid_blocks ? (unsigned)grid_blocks : 8u * (unsigned)std::max(ctx->cu_count, 1);
     std::copy(resolution, resolution + NL, S.gamma);
     S.ratio = layer_ratio;
     S.n0 = n;

@@ -372,9 +372,17 @@ int sqgr_leiden_multiplex_info(int64_t* out_info) {
 int sqgr_leiden_multiplex(sqgr_ctx* ctx, int64_t n, const int64_t* indptr0, const int32_t* indices0, const int32_t* weights0,
                           const int64_t* indptr1, const int32_t* indices1, const int32_t* weights1, double resolution0, double resolution1,
                           double layer_ratio, int32_t n_iterations, int32_t* out_labels, int64_t* out_stats) {
+    return sqgr_leiden_multiplex_hook(ctx, n, indptr0, indices0, weights0, indptr1, indices1, weights1, resolution0, resolution1, layer_ratio,
+                                      n_iterations, out_labels, out_stats, 0);
+}
+
+int sqgr_leiden_multiplex_hook(sqgr_ctx* ctx, int64_t n, const int64_t* indptr0, const int32_t* indices0, const int32_t* weights0,
+                               const int64_t* indptr1, const int32_t* indices1, const int32_t* weights1, double resolution0, double resolution1,
+                               double layer_ratio, int32_t n_iterations, int32_t* out_labels, int64_t* out_stats, int32_t grid_blocks) {
     const int64_t* const indptr[MX_LAYERS] = {indptr0, indptr1};
     const int32_t* const indices[MX_LAYERS] = {indices0, indices1};
     const int32_t* const weights[MX_LAYERS] = {weights0, weights1};
     const double resolution[MX_LAYERS] = {resolution0, resolution1};
-    return leiden_run<MX_LAYERS, TwoLayers>(ctx, n, indptr, indices, weights, resolution, layer_ratio, n_iterations, out_labels, out_stats);
+    return leiden_run<MX_LAYERS, TwoLayers>(ctx, n, indptr, indices, weights, resolution, layer_ratio, n_iterations, out_labels, out_stats,
+                                            grid_blocks);
 }

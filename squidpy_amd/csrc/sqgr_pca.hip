@@ -235,6 +235,16 @@ int sqgr_pca_info(int64_t* out_info) {
     return SQGR_OK;
 }
 
+int sqgr_pca_geometry(int64_t n, int32_t D, int64_t* out) {
+    SQGR_REQUIRE(out, "null argument");
+    SQGR_REQUIRE(n >= 2 && n < ((int64_t)1 << 31) && D >= 2 && D <= PCA_MAX_D, "sqgr_pca_geometry: n=%lld D=%d", (long long)n, D);
+    const PcaGeometry q = pca_geometry(n, D);
+    const int64_t v[10] = {q.nt, q.npairs, q.mean_rows, q.scat_rows, q.mean_chunks, q.scat_chunks, PCA_CHUNK, PCA_MAX_CHUNKS, PCA_TARGET_BLOCKS,
+                           PCA_TILE};
+    std::copy(v, v + 10, out);
+    return SQGR_OK;
+}
+
 int sqgr_pca_create(sqgr_ctx* ctx, int64_t n, int32_t D, sqgr_pca** out) {
     SQGR_REQUIRE(ctx && out, "null argument");
     if (n < 2 || n >= ((int64_t)1 << 31) || D < 2 || D > PCA_MAX_D) {

@@ -218,3 +218,34 @@ def cases() -> list[dict]:
     lab[rng.choice(3000, 20, replace=False)] = -1
     out.append(dict(name="knn3000", conn=knn_directed(xy, 6, rng), codes=lab, n_cls=7))
     return out
+
+
+# ------------------------------------------------------------------------- the lattice above one trip of the default grid
+def lattice_graph(side: int) -> sp.csr_matrix:
+    """4-neighbour ``side`` x ``side`` lattice, node ``y * side + x``."""
+    idx = np.arange(side * side, dtype=np.int64).reshape(side, side)
+    r = np.r_[idx[:, :-1].ravel(), idx[:-1, :].ravel()]
+    c = np.r_[idx[:, 1:].ravel(), idx[1:, :].ravel()]
+    adj = sp.csr_matrix((np.ones(2 * len(r), np.float32), (np.r_[r, c], np.r_[c, r])), shape=(side * side, side * side))
+    adj.sort_indices()
+    return adj
+
+
+def lattice_codes(side: int) -> np.ndarray:
+    """Group 0 = the first column, group 1 = the far corner, everything else in no group."""
+    codes = np.full((side, side), -1, np.int32)
+    codes[:, 0] = 0
+    codes[side - 1, side - 1] = 1
+    return codes.ravel()
+
+
+def lattice_closed_form(side: int) -> tuple:
+    """Hop distances on the lattice are Manhattan distances.  Group 0: node (x, y) lies x hops away, x = 1 .. side - 1 in each of
+    ``side`` rows.  Group 1: (side - 1 - x) + (side - 1 - y) hops; with u = side - 1 - x, v = side - 1 - y the sum of u + v over the
+    square is side^2 (side - 1).  The corner node itself is a member of group 1 but lies side - 1 hops from group 0; the first column
+    lies u + v = (side - 1) + v hops from group 1 and is counted there."""
+    s = side
+    adjacent = np.array([s, 2], np.int64)
+    dist_sum = np.array([s * (s * (s - 1) // 2), s * s * (s - 1)], np.int64)
+    reached = np.array([s * (s - 1), s * s - 1], np.int64)
+    return adjacent, dist_sum, reached, 2 * (s - 1)

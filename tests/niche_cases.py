@@ -43,8 +43,15 @@ CASES: dict[str, Case] = {
     "dups": Case(500, 3, 4, 9010, 3.0, dups=40, why="40 identical rows (a near-singular component)"),
     "offset1e3": Case(2000, 4, 4, 9011, 3.0, offset=1e3, why="data shifted by 1e3: the centred covariance form"),
     "maxiter5": Case(3000, 5, 5, 9012, 1.0, max_iter=5, why="max_iter=5 reached without convergence"),
+    # launch-geometry seams of csrc/sqgr_gmm.hip (gmm_geometry; tests/test_launch_geometry_cpu.py pins what binds), each at the smallest n at
+    # which its caps bind
+    "cap_rows": Case(262_657, 3, 4, 9101, 8.0, max_iter=6,
+                     why="an E-step block walks two tiles, the last block one tile of one row; k_gmm_sums and k_gmm_cov at their chunk caps"),
+    "cap_cov_k64": Case(16_897, 4, 64, 9113, 25.0, max_iter=10,
+                        why="k_gmm_cov at its cap of 2048 / 64 chunks while k_gmm_sums is not; the last tile has one row"),
 }
 NAMES = tuple(CASES)
+GEOMETRY_CASES = ("cap_rows", "cap_cov_k64")  # stop at max_iter or not as sklearn does; their margins to tol are pinned on the CPU
 
 
 @functools.lru_cache(maxsize=None)
@@ -106,7 +113,8 @@ def reference(name: str, random_state: int) -> Reference:
 
 def close(got: np.ndarray, ref: np.ndarray) -> tuple[float, float]:
     """``(max |got - ref|, bound)`` with the bound of the GPU tests: ``1e-9 * max(1, max |ref|)``.  A correct implementation differs
-    from sklearn by rounding order only (<= 3e-12 against values of order 1 to 1e3); the smallest effect of a real error (a dropped
+    from sklearn by rounding order only (<= 3e-12 against values of order 1 to 1e3; <= 2.0e-10 in a covariance of ``cap_cov_k64``,
+    whose values reach 217 on that seed, where two CPU orders differ by 7e-11); the smallest effect of a real error (a dropped
     ``reg_covar``, a wrong ``nk`` guard, one EM step too many or too few) is >= 1e-6 in a covariance."""
     got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
     return float(np.max(np.abs(got - ref))) if ref.size else 0.0, 1e-9 * max(1.0, float(np.max(np.abs(ref))) if ref.size else 0.0)

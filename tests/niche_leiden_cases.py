@@ -65,6 +65,16 @@ def _ring_of_cliques(weights: tuple[float, float] = (1.0, 1.0)) -> tuple[sparse.
     return _sym(48, r, c, w), np.repeat(np.arange(8), 6)
 
 
+def big_ring_graph(q: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``_ring_of_cliques`` with ``q`` cliques and unit weights, built without a Python loop over the cliques, as ``graph`` returns it."""
+    i, j = np.triu_indices(6, 1)
+    base = 6 * np.arange(q, dtype=np.int64)[:, None]
+    r = np.r_[(base + i[None, :]).ravel(), base.ravel() + 5]
+    c = np.r_[(base + j[None, :]).ravel(), 6 * ((np.arange(q, dtype=np.int64) + 1) % q)]
+    a = _sym(6 * q, r, c)
+    return a.indptr.astype(np.int64), a.indices.astype(np.int32), LO.quantise(a)
+
+
 def _disjoint_cliques() -> tuple[sparse.csr_matrix, np.ndarray]:
     r, c, start, planted = [], [], 0, []
     for q, size in enumerate((7, 5, 5, 3, 1, 1)):

@@ -46,6 +46,15 @@ CASES = {
     "float32": Case(350, 33, 16, 10, float32=True),
 }
 
+# Launch-geometry seams of csrc/sqgr_pca.hip (pca_geometry): used by the moments and projection tests only — the host eigenproblem of
+# a 4096 x 4096 matrix is not what they are about.  tests/test_launch_geometry_cpu.py pins what binds in each.
+SEAM_CASES = {
+    "mean_cap": Case(524_289, 3, 2, 21),        # column sums in chunks of 1024 rows (513 of them, the last of one row); scatter likewise
+    "limit_d4096": Case(1_025, 4096, 64, 22),   # the largest D: 64 tiles, 2 080 tile pairs, one chunk whose last sub-tile has one row
+    "capped_chunks": Case(5_633, 1100, 50, 23), # 171 tile pairs cap the scatter at 11 < 12 chunks: 6 chunks of 1024 rows, the last of 513
+}
+SEAM_NAMES = tuple(SEAM_CASES)
+
 
 def chunk_rows() -> int:
     """Rows of a chunk of the scatter kernel, from the library (``sqgr_pca_info``: no device needed)."""
@@ -62,6 +71,8 @@ def chunk_cases(chunk: int) -> dict[str, Case]:
 def case(name: str) -> Case:
     if name in CASES:
         return CASES[name]
+    if name in SEAM_CASES:
+        return SEAM_CASES[name]
     try:
         chunk = chunk_rows()
     except OSError:
@@ -90,6 +101,16 @@ def data(name: str) -> np.ndarray:
     x = np.ascontiguousarray(x, dtype=np.float32 if c.float32 else np.float64)
     x.setflags(write=False)
     return x
+
+
+@functools.lru_cache(maxsize=None)
+def seam_components(name: str) -> np.ndarray:
+    """``c`` orthonormal rows of length ``D`` from the case's seed (read-only): components for the projection without an eigenproblem."""
+    c = SEAM_CASES[name]
+    basis, _ = np.linalg.qr(np.random.default_rng(c.seed + 1000).normal(0.0, 1.0, (c.d, c.c)))
+    out = np.ascontiguousarray(basis.T)
+    out.setflags(write=False)
+    return out
 
 
 def data64(name: str) -> np.ndarray:

@@ -61,11 +61,14 @@ def components_of(scatter: np.ndarray, n: int, c: int) -> tuple[np.ndarray, np.n
 def project(x: np.ndarray, mean: np.ndarray, components: np.ndarray) -> np.ndarray:
     """``out[i][r] = sum_j (x[i][j] - mean[j]) * components[r][j]``, j ascending."""
     x = np.asarray(x, dtype=np.float64)
-    out = np.zeros((len(x), len(components)), dtype=np.float64)
+    out = np.zeros((len(components), len(x)), dtype=np.float64)  # transposed: the rows of x run along the contiguous axis
+    prod = np.empty_like(out)  # one product array for all j: the same two rounded array operations per column, without 2 D allocations
+    xt, ct = np.ascontiguousarray(x.T), np.ascontiguousarray(np.asarray(components, dtype=np.float64).T)  # column j of either, contiguous
     for j in range(x.shape[1]):
-        diff = x[:, j] - mean[j]
-        out = out + diff[:, None] * components[:, j][None, :]
-    return out
+        diff = xt[j] - mean[j]
+        np.multiply(ct[j][:, None], diff[None, :], out=prod)
+        np.add(out, prod, out=out)
+    return np.ascontiguousarray(out.T)
 
 
 def pca(x: np.ndarray, c: int | None = None) -> PCA:
@@ -120,6 +123,29 @@ def exact_scatter_and_bound(x: np.ndarray, mean: np.ndarray) -> tuple[np.ndarray
             e = ((hi[:, a] * hi[:, b] - p) + hi[:, a] * lo[:, b] + lo[:, a] * hi[:, b]) + lo[:, a] * lo[:, b]  # p + e == the exact product
             out[a, b] = out[b, a] = math.fsum(np.concatenate([p, e]))
             bound[a, b] = bound[b, a] = g * np.abs(p).sum()
+    return out, bound
+
+
+def exact_scatter_pairs_and_bound(x: np.ndarray, mean: np.ndarray, pairs: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """``exact_scatter_and_bound`` for the entries ``pairs`` (m, 2) only: ``(exact[m], bound[m])``."""
+    x = np.asarray(x, dtype=np.float64)
+    g = gamma(len(x) + 2)
+    split = 134217729.0  # 2^27 + 1
+    cols = np.unique(pairs)
+    z = {int(j): x[:, j] - mean[j] for j in cols}
+    parts = {}
+    for j, zj in z.items():
+        zs = zj * split
+        hi = zs - (zs - zj)
+        parts[j] = (hi, zj - hi)
+    out, bound = np.zeros(len(pairs)), np.zeros(len(pairs))
+    for i, (a, b) in enumerate(pairs):
+        a, b = int(a), int(b)
+        (ha, la), (hb, lb) = parts[a], parts[b]
+        p = z[a] * z[b]
+        e = ((ha * hb - p) + ha * lb + la * hb) + la * lb  # p + e == the exact product
+        out[i] = math.fsum(np.concatenate([p, e]))
+        bound[i] = g * np.abs(p).sum()
     return out, bound
 
 

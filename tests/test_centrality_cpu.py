@@ -179,6 +179,17 @@ def test_oracle_closed_forms():
     assert (GOLD["hub5000/cc"][1:41] == 1.0).all() and np.diff(GOLD["hub5000/adj_indptr"])[0] == 5000
 
 
+@pytest.mark.parametrize("side", [2, 7, 40])
+def test_lattice_closed_form_equals_the_oracle(side):
+    """The closed form the GPU test of the 640 000-node lattice relies on, against the BFS restatement at the same construction."""
+    adj, codes = CO.build_graph(CO.lattice_graph(side)), CO.lattice_codes(side)
+    assert adj.shape[0] == side * side and adj.nnz == 4 * side * (side - 1)
+    got, want = CO.group_bfs(adj, codes, 2), CO.lattice_closed_form(side)
+    for a, b in zip(got[:3], want[:3]):
+        assert np.array_equal(a, b)
+    assert got[3] == want[3]
+
+
 def test_unreached_component_adds_nothing():
     """Group 0 of the two-component cases has no member in the second component: those nodes add 0 to its distance sum."""
     adj, codes = literal_adj("comp70_k3"), GOLD["comp70_k3/codes"]

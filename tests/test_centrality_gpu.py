@@ -8,7 +8,12 @@ a 300-node path in natural and random node order (an in-place sweep fails in nat
 70-node two-component graph with an isolated node at K = 3, 64, 65, 130 (word and pass boundaries, unreached nodes, NaN labels,
 empty categories), hex lattices of 2000, 257 and 1025 nodes (block edges), stored zeros / cancelling weights / a diagonal, a hub of
 degree 5000 next to a clique and leaves (the wave-per-row gather, skewed list intersections), a directed weighted kNN graph with
-self loops through the front end; a 70 001-node path against its closed form; and the refusals."""
+self loops through the front end; a 70 001-node path against its closed form; and the refusals.
+
+Launch geometry: ``k_bfs_level`` caps its grid at 8 x compute units and strides over the nodes.  Every case above runs again through
+``sqgr_group_bfs_hook`` with 1 and 3 blocks (a block then makes several trips, the partial last one included), the long path with 3; a
+hub whose 301-entry row — the wave-cooperative gather — lies in the second trip of the only block; and, without the hook, a square
+lattice of more nodes than the default grid covers in one trip, against the closed form of its hop distances."""
 
 from __future__ import annotations
 
@@ -86,9 +91,24 @@ def test_frame_equals_networkx_and_literal_source(name):
     assert np.array_equal(before.indices, after.indices) and np.array_equal(before.data, after.data)
 
 
-def test_long_path_closed_form():
-    """Path of 70 001 nodes, group {0}: node v lies v hops away, dist_sum = n (n - 1) / 2 = 2 450 035 000 — neither the level nor a
-    distance fits 16 bits, the sum does not fit 32."""
+@pytest.mark.parametrize("grid_blocks", [1, 3])
+@pytest.mark.parametrize("name", CASES)
+def test_device_integers_do_not_depend_on_the_grid(name, grid_blocks):
+    """The same integers when 1 or 3 blocks stride over all nodes (``sqgr_group_bfs_hook``)."""
+    adj, codes, K, (adjacent, dist_sum, reached, levels), _ = restated(name)
+    ctx = default_context()
+    g = Graph(ctx, adj, with_data=False)
+    try:
+        got = group_bfs(ctx, g, codes, K, grid_blocks=grid_blocks)
+    finally:
+        g.close()
+    assert np.array_equal(got[0], adjacent)
+    assert np.array_equal(got[1], dist_sum)
+    assert np.array_equal(got[2], reached)
+    assert got[3] == levels
+
+
+def _long_path(grid_blocks: int) -> None:
     n = 70_001
     g_host = CO.path_graph(n)
     codes = np.full(n, -1, np.int32)
@@ -96,13 +116,68 @@ def test_long_path_closed_form():
     ctx = default_context()
     g = Graph(ctx, g_host, with_data=False)
     try:
-        adjacent, dist_sum, reached, levels = group_bfs(ctx, g, codes, 1)
+        adjacent, dist_sum, reached, levels = group_bfs(ctx, g, codes, 1, grid_blocks=grid_blocks)
         tri = graph_triangles(ctx, g)
     finally:
         g.close()
     print("dist_sum", dist_sum, "levels", levels)
     assert dist_sum[0] == n * (n - 1) // 2 and adjacent[0] == 1 and reached[0] == n - 1 and levels == n - 1
     assert not tri.any()
+
+
+def test_long_path_closed_form():
+    """Path of 70 001 nodes, group {0}: node v lies v hops away, dist_sum = n (n - 1) / 2 = 2 450 035 000 — neither the level nor a
+    distance fits 16 bits, the sum does not fit 32."""
+    _long_path(0)
+
+
+def test_long_path_closed_form_with_three_blocks():
+    """The same path when 3 blocks stride over it: 92 trips per block and level."""
+    _long_path(3)
+
+
+def test_long_row_in_a_second_trip():
+    """Path 0 - 1 - ... - 299 - hub 300, the hub's 300 leaves are nodes 301 .. 600: the hub's row has 301 entries (more than the 128
+    up to which a lane walks its row alone) and, with one block of 256 threads, lies in that block's second trip.  Group 0 = the far
+    end of the path, group 1 = one leaf: the hub gathers its row by the wave at every level until group 0 arrives at level 300."""
+    n, hub = 601, 300
+    r = np.r_[np.arange(hub), np.full(300, hub)]
+    c = np.r_[np.arange(1, hub + 1), np.arange(hub + 1, n)]
+    adj = sp.csr_matrix((np.ones(2 * len(r), np.float32), (np.r_[r, c], np.r_[c, r])), shape=(n, n))
+    adj.sort_indices()
+    assert np.diff(adj.indptr)[hub] == 301 and hub >= 256
+    codes = np.full(n, -1, np.int32)
+    codes[0], codes[450] = 0, 1
+    expected = CO.group_bfs(adj, codes, 2)
+    assert expected[3] == 301 and expected[2].tolist() == [n - 1, n - 1]
+    ctx = default_context()
+    g = Graph(ctx, adj, with_data=False)
+    try:
+        for grid_blocks in (1, 0):
+            got = group_bfs(ctx, g, codes, 2, grid_blocks=grid_blocks)
+            for a, b in zip(got[:3], expected[:3]):
+                assert np.array_equal(a, b), grid_blocks
+            assert got[3] == expected[3]
+    finally:
+        g.close()
+
+
+def test_lattice_above_one_trip_of_the_default_grid():
+    """``side`` is chosen so that side^2 nodes exceed what 8 x compute units blocks of 256 threads cover in one trip (800 on 256
+    compute units: 640 000 nodes, 1 598 levels): the default launch's blocks make a second, partial trip."""
+    ctx = default_context()
+    cu = ctx.device_info()["cu_count"]
+    side = int(np.ceil(np.sqrt(8 * cu * 256))) + 76
+    assert side * side > 8 * cu * 256
+    adj, codes = CO.lattice_graph(side), CO.lattice_codes(side)
+    g = Graph(ctx, adj, with_data=False)
+    try:
+        adjacent, dist_sum, reached, levels = group_bfs(ctx, g, codes, 2)
+    finally:
+        g.close()
+    want = CO.lattice_closed_form(side)
+    print("side", side, "dist_sum", dist_sum, "levels", levels)
+    assert np.array_equal(adjacent, want[0]) and np.array_equal(dist_sum, want[1]) and np.array_equal(reached, want[2]) and levels == want[3]
 
 
 def test_closed_forms_on_the_device():

@@ -8,7 +8,11 @@
 - ``calculate_niche_neighborhood`` / ``calculate_niche_utag`` end to end on a 30 x 30 hexagonal lattice with 5 planted cell-type domains
   and 20 genes: columns written, equal to the chain run step by step through the public functions, and with ``library_key`` equal to
   two separate runs on the sub-objects.
-- The device's refusals name the property that failed."""
+- The device's refusals name the property that failed.
+- Launch geometry: every case at its first resolution again through ``sqgr_leiden_hook`` with 1 and 3 blocks (``k_best`` then takes
+  n / 4 and n / 12 trips per block and reuses its LDS tables and per-wave slots; the element kernels stride too): the bytes of the
+  default call.  Without the hook, a ring of six-cliques of more rows than the default grid's waves hold in one trip, against the
+  restatement."""
 
 from __future__ import annotations
 
@@ -52,6 +56,34 @@ def test_device_equals_the_restatement(ctx, name, resolution):
     assert labels.tobytes() == again.tobytes() and stats == stats_again
     if name in LC.PLANTED:
         assert np.array_equal(labels, LC.planted(name))
+
+
+@pytest.mark.parametrize("grid_blocks", [1, 3])
+@pytest.mark.parametrize("name", LC.CASES)
+def test_result_does_not_depend_on_the_grid(ctx, name, grid_blocks):
+    resolution = (LC.PLANTED_RESOLUTIONS if name in LC.PLANTED else LC.RESOLUTIONS)[0]
+    graph = LC.graph(name)
+    labels, stats = _lib.leiden(ctx, *graph, resolution, -1, grid_blocks=grid_blocks)
+    expected_labels, expected_stats = LC.expected(name, resolution)
+    assert labels.dtype == np.int32 and np.array_equal(labels, expected_labels)
+    assert stats == expected_stats
+    default, default_stats = _lib.leiden(ctx, *graph, resolution, -1)
+    assert labels.tobytes() == default.tobytes() and stats == default_stats
+
+
+@pytest.mark.parametrize("resolution", [1.0, 50.0])
+def test_ring_above_one_trip_of_the_default_grid(ctx, resolution):
+    """q six-cliques on a ring, q chosen so that n = 6 q exceeds the 4 rows x 8 x compute units blocks that ``k_best`` covers in one
+    trip (n = 12 000 > 8 192 on 256 compute units).  The planted cliques are not what these resolutions return: the restatement is
+    the reference."""
+    cu = ctx.device_info()["cu_count"]
+    q = max(2000, (4 * 8 * cu) // 6 + 300)
+    graph = LC.big_ring_graph(q)
+    assert graph[0].shape[0] - 1 == 6 * q > 4 * 8 * cu
+    labels, stats = _lib.leiden(ctx, *graph, resolution, -1)
+    expected_labels, expected_stats = LO.leiden(*graph, resolution, -1)
+    print("ring", q, "resolution", resolution, stats)
+    assert np.array_equal(labels, expected_labels) and stats == expected_stats
 
 
 @pytest.mark.parametrize("n_iterations", [1, 2])

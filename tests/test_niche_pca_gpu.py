@@ -8,6 +8,10 @@
 - ``niche_pca`` scores against sklearn's ``PCA(svd_solver="arpack")`` within ``tol_j = C eps lambda_1 / gap_j max |scores|``, ``C`` = 171
   as measured and derived in tests/test_niche_pca_cpu.py.
 - The device-side fill of the feature blocks ``==`` the host round trip, bit for bit.
+- Launch-geometry seams (``PC.SEAM_CASES``: chunks of more than 512 rows, the chunk cap of the scatter, D = 4096): means within the same
+  exact bound; the scatter of the narrow case exactly over all pairs, of the two wide cases as a whole against float64 ``z.T @ z``
+  within ``2 gamma(n + 2) |z|.T @ |z|`` (device and BLAS each lie within one ``gamma`` of the exact value) and exactly on a seeded sample
+  of 2 000 entries plus the four corners; exact symmetry; two calls, the same bytes; the projection bit for bit on seeded orthonormal rows.
 - The chain's labels ``==`` sklearn's chain behind the reference's literal features (tests/golden/niche_pca_reference.npz)."""
 
 from __future__ import annotations
@@ -104,6 +108,72 @@ def test_scores_agree_with_sklearn(name):
     assert got.mean.tobytes() == device_moments(name)[0][0].tobytes()
     again = sq.gr.niche_pca(PC.data(name), c.c)
     assert all(a.tobytes() == b.tobytes() for a, b in zip(got, again))
+
+
+# ---- launch-geometry seams ---------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def seam_run(name: str):
+    """``(mean, scatter, second call returned the same bytes, projection)`` of a seam case from the device."""
+    x, c = PC.data(name), PC.case(name)
+    pca = DevicePCA(default_context(None), c.n, c.d)
+    try:
+        pca.upload(x)
+        mean, scatter = pca.moments()
+        mean2, scatter2 = pca.moments()
+        same = mean.tobytes() == mean2.tobytes() and scatter.tobytes() == scatter2.tobytes()
+        del scatter2
+        return mean, scatter, same, pca.project(PC.seam_components(name))
+    finally:
+        pca.close()
+
+
+@pytest.mark.parametrize("name", PC.SEAM_NAMES)
+def test_seam_means_within_the_order_free_bound(name):
+    mean = seam_run(name)[0]
+    want, bound = O.exact_mean_and_bound(PC.data64(name))
+    print(name, "mean error / bound", float(np.max(np.abs(mean - want) / np.maximum(bound, 1e-300))), "max |error|", float(np.abs(mean - want).max()))
+    assert (np.abs(mean - want) <= bound).all()
+
+
+def test_seam_scatter_of_the_narrow_case_exactly():
+    mean, scatter, same, _ = seam_run("mean_cap")
+    want, bound = O.exact_scatter_and_bound(PC.data64("mean_cap"), mean)
+    print("mean_cap scatter error / bound", float(np.max(np.abs(scatter - want) / np.maximum(bound, 1e-300))), "max |error|",
+          float(np.abs(scatter - want).max()), "max |S|", float(np.abs(want).max()))
+    assert (np.abs(scatter - want) <= bound).all()
+    assert np.array_equal(scatter, scatter.T) and same
+
+
+@pytest.mark.parametrize("name", ("limit_d4096", "capped_chunks"))
+def test_seam_scatter_of_a_wide_case(name):
+    c = PC.case(name)
+    mean, scatter, same, _ = seam_run(name)
+    assert np.array_equal(scatter, scatter.T) and same
+    z = PC.data64(name) - mean
+    blas = z.T @ z
+    az = np.abs(z)
+    bound = 2.0 * O.gamma(c.n + 2) * (az.T @ az)
+    err = np.abs(scatter - blas)
+    print(name, "whole scatter vs float64 z.T @ z: error / bound", float(np.max(err / np.maximum(bound, 1e-300))), "max |error|", float(err.max()),
+          "max |S|", float(np.abs(blas).max()))
+    assert (err <= bound).all()
+    rng = np.random.default_rng(c.seed + 2000)
+    pairs = np.r_[rng.integers(0, c.d, (2000, 2)), [[0, 0], [0, c.d - 1], [c.d - 1, 0], [c.d - 1, c.d - 1]]]
+    want, exact_bound = O.exact_scatter_pairs_and_bound(PC.data64(name), mean, pairs)
+    got = scatter[pairs[:, 0], pairs[:, 1]]
+    print(name, "sampled entries vs exact: error / bound", float(np.max(np.abs(got - want) / np.maximum(exact_bound, 1e-300))), "max |error|",
+          float(np.abs(got - want).max()))
+    assert (np.abs(got - want) <= exact_bound).all()
+
+
+@pytest.mark.parametrize("name", PC.SEAM_NAMES)
+def test_seam_projection_equals_the_restatement_bit_for_bit(name):
+    c = PC.case(name)
+    mean, _, _, got = seam_run(name)
+    components = PC.seam_components(name)
+    assert components.shape == (c.c, c.d) and np.abs(components @ components.T - np.eye(c.c)).max() < 1e-12
+    want = O.project(PC.data64(name), mean, components)
+    assert got.shape == (c.n, c.c) and got.tobytes() == want.tobytes()
 
 
 def test_default_n_comps_and_column_upload():

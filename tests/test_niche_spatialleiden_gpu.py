@@ -6,6 +6,8 @@
   returns the same bytes.
 - ``sqgr_leiden_multiplex(G, empty)`` returns the bytes of ``sqgr_leiden(G)``.
 - Fixed iteration counts; the device's refusals name the layer and the property.
+- Launch geometry: every case at its first resolution pair and ratio again through ``sqgr_leiden_multiplex_hook`` with 1 and 3 blocks:
+  the restatement's labels and stats and the bytes of the default call.
 - The drop-in end to end on a 30 x 30 hexagonal lattice after ``sq.gr.niche_neighbors``: columns written, equal to
   ``niche_spatialleiden`` per resolution, and with ``library_key`` equal to two runs on the sub-objects."""
 
@@ -52,6 +54,20 @@ def test_device_equals_the_restatement(ctx, name, resolutions, ratio):
     assert stats == expected_stats
     again, stats_again = _lib.leiden_multiplex(ctx, *layers, resolutions, ratio, -1)
     assert labels.tobytes() == again.tobytes() and stats == stats_again
+
+
+@pytest.mark.parametrize("grid_blocks", [1, 3])
+@pytest.mark.parametrize("name", MC.CASES)
+def test_result_does_not_depend_on_the_grid(ctx, name, grid_blocks):
+    resolutions, ratio = MC.RESOLUTIONS[0], MC.RATIOS[0]
+    assert (name, resolutions, ratio) in MC.COMBOS
+    layers = MC.layers(name)
+    labels, stats = _lib.leiden_multiplex(ctx, *layers, resolutions, ratio, -1, grid_blocks=grid_blocks)
+    expected_labels, expected_stats = MC.expected(name, resolutions, ratio)
+    assert labels.dtype == np.int32 and np.array_equal(labels, expected_labels)
+    assert stats == expected_stats
+    default, default_stats = _lib.leiden_multiplex(ctx, *layers, resolutions, ratio, -1)
+    assert labels.tobytes() == default.tobytes() and stats == default_stats
 
 
 @pytest.mark.parametrize("resolution", LC.RESOLUTIONS)
