@@ -74,7 +74,7 @@ struct sqgr_ctx {
     // asked for; valid until the next request for the same slot.  Single stream, calls are synchronous: no aliasing.
     std::vector<std::pair<void*, size_t>> scratch;
     int scratch_get(int slot, size_t bytes, void** out);
-    sqgr::CtxCache* autocorr_lists = nullptr;  // bucket lists of the last permutation set (sqgr_autocorr.hip)
+    sqgr::CtxCache* autocorr_lists = nullptr;  // bucket lists of the last permutation set (sqgr_autocorr_lists.hip)
 
     int timer_id(const char* name);
     int begin_launch(const char* name, sqgr::TimedLaunch* tl, hipStream_t st);

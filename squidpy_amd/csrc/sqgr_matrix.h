@@ -1,6 +1,6 @@
 #pragma once
-// The expression matrix resident on the device (sqgr_matrix_create*, defined in sqgr_autocorr.hip) and the one column
-// expansion that every consumer of a column LIST shares (spatial_autocorr's feature blocks, sepal's gene batches).
+// The expression matrix resident on the device (sqgr_matrix_create*, sqgr_matrix.hip) and the expansions of its columns into a
+// gene-major float64 block that its consumers share (spatial_autocorr's feature blocks, sepal's gene batches, niche, PCA).
 #include "sqgr_common.h"
 
 // The expression matrix resident on the device (uploaded once per call): dense row-major float64 / float32, or scipy's
@@ -26,7 +26,12 @@ struct sqgr_matrix {
 };
 
 namespace sqgr {
+constexpr int MATRIX_TILE = 64;  // the dense expansions transpose tiles of 64 cells x 64 columns through LDS
 // X[g * n_rows + i] = (double) m[i, dev_cols[g]] for g < gc: dev_cols is a device array; a CSR matrix needs its by-column twin
 // (m->ensure_by_column()) first.  Enqueued on `st`.
 hipError_t expand_column_list(const sqgr_matrix* m, const int32_t* dev_cols, int gc, double* X, hipStream_t st);
+// The same for the contiguous columns [col0 + g0, col0 + g0 + gc) of any kind of matrix (no twin needed).
+hipError_t expand_column_range(const sqgr_matrix* m, int64_t col0, int64_t g0, int gc, double* X, hipStream_t st);
+// ... and of a dense float64 cell-major device array D[n][ld] that is not a sqgr_matrix: X[g * n + i] = D[i * ld + g0 + g].
+hipError_t expand_dense_f64(const double* D, int64_t ld, int64_t n, int64_t g0, int gc, double* X, hipStream_t st);
 }  // namespace sqgr

@@ -1,4 +1,4 @@
-"""Design model behind the list schedules of csrc/sqgr_autocorr.hip (k_bucket_order / _joint / _steps): LDS cycles per step and
+"""Design model behind the list schedules of csrc/sqgr_autocorr_lists.hip (k_bucket_order / _joint / _steps): LDS cycles per step and
 `ds_read_b128` service group (16 lanes) for the two operand reads of the LDS-bucketed permutation dot, on random lists.
 
 A pair of a list is (class of its Z row, class of its Y row), class = row index mod 16 = the 4-bank slot of the 16-byte row; a group
