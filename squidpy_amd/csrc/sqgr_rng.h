@@ -82,10 +82,18 @@ typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
 // round function: 16-bit multiply-add / xor-shift / multiply, of which the TOP `16 - sh` bits are returned (the best mixed
 // ones, and already reduced to the digit's power-of-two range: no mask afterwards); arithmetic modulo 2^16.
-// 5 packed ops: v_pk_mad_u16, v_pk_lshrrev_b16, v_xor_b32, v_pk_mul_lo_u16, v_pk_lshrrev_b16.
+// 5 ops: v_pk_mad_u16, v_lshrrev_b32, v_bitop3_b32, v_pk_mul_lo_u16, v_pk_lshrrev_b16.
+// x ^= x >> 7 in both 16-bit halves, on the bit-cast word: a 32-bit shift moves the high half's seven low bits into bits 9-15 of
+// the low half, and the mask — the nine significant bits of x >> 7 per half — removes exactly those.  One 32-bit shift and one
+// three-input bit operation instead of a packed shift and an xor (tests/test_shuffle_carry_cpu.py).  The final x >> sh stays
+// packed: its shift count is not a constant.
+__device__ __forceinline__ u16x2 xorshift7_2(u16x2 x) {
+    const uint32_t w = __builtin_bit_cast(uint32_t, x);
+    return __builtin_bit_cast(u16x2, w ^ ((w >> 7) & 0x01FF01FFu));
+}
 __device__ __forceinline__ u16x2 feistel_F2(u16x2 v, u16x2 k, u16x2 sh) {
     u16x2 x = v * (u16x2)(FEISTEL_C1) + k;
-    x ^= x >> (u16x2)(7);
+    x = xorshift7_2(x);
     x *= (u16x2)(FEISTEL_C2);
     return x >> sh;
 }

@@ -264,7 +264,7 @@ static_assert(SHUF_TAB_MAX_A * 4u <= (1u << 12), "k_shuffle_tab carries the high
 // per evaluation); with C1 in a VGPR the key is the instruction's scalar operand.
 __device__ __forceinline__ u16x2 shuf_tab_F2(u16x2 v, u16x2 k, u16x2 sh, u16x2 c1) {
     u16x2 x = v * c1 + k;
-    x ^= x >> (u16x2)(7);
+    x = xorshift7_2(x);
     x *= (u16x2)(FEISTEL_C2);
     return x >> sh;
 }
@@ -296,6 +296,16 @@ __device__ __forceinline__ uint32_t first_label(uint32_t e, uint32_t bpk, uint32
         : "v"(e), "v"(bpk), "v"(zero)
         : "vcc");
     return word;
+}
+// The FIX instance's form of a two-field block-table entry  first | boundary << 16  (LabelShuffler::create; it reads no sentinel
+// entry):  first << 16 | (2^16 - boundary) mod 2^16,  and  (first + 1) << 16  for a boundary of 0.  A low digit b < B <= 2^14 added
+// to it carries out of the low half exactly when b >= boundary (0xFFFF, "none", leaves 1 there: never), so byte 2 of the sum is
+// first + (b >= boundary) — one add per label in place of the compare / add-with-carry pair, no vcc (tests/test_shuffle_carry_cpu.py).
+// LabelShuffler::create never writes a boundary of 0 (a label that starts on offset 0 is the block's first label; a one-event entry
+// needs ev_pos > 0), so that branch is a guard no table reaches on the device; the CPU test covers it.
+__device__ __forceinline__ uint32_t carry_entry(uint32_t e) {
+    const uint32_t first = e & 0xFFu, boundary = e >> 16;
+    return boundary == 0u ? (first + 1u) << 16 : first << 16 | ((0x10000u - boundary) & 0xFFFFu);
 }
 
 // The tables of ALL row pairs of a launch, once (k_shuffle_tab<.., PRETAB = true> copies them): tabs[y][g][a][t] for row pair y =
@@ -332,6 +342,9 @@ __global__ __launch_bounds__(256) void k_shuffle_tab_build(const uint32_t* __res
 // kernel, writes exactly those from the inverse networks.  Here the entries of the blocks that reach past rank n (the partial
 // block, which eligibility requires to end in label K - 1, and with B clamped to 16 whole blocks behind it) are replaced while
 // the table is copied into LDS by  K - 1 | 0xFFFF << 16 : every byte this kernel stores is a label < K, whatever runs later.
+// The same copy stores every entry in carry form (carry_entry): a label is one add, a word's four labels are assembled by two
+// v_perm_b32 and an or — seven instructions per word, none of them on vcc, where the two-field look-up takes eight and four
+// hand-written wait states.
 // PRETAB (launch_shuffle_raw decides; SQGR_SHUFFLE_PRETAB): T depends on the row pair's sigma keys alone, yet every one of the
 // launch's blocks of a row pair (62 at 1e6 spots x 160 rows) built it again.  k_shuffle_tab_build, launched in front of this kernel,
 // computes the tables of all row pairs once into `tabs` — [row pair][g][a][t], the LDS image — and a block copies its 2 * A * 32
@@ -347,7 +360,7 @@ __global__ __launch_bounds__(SHUF_TAB_THREADS, 8) void k_shuffle_tab(int64_t n, 
     if constexpr (FIX) {  // (the boundaries are the exact route's: not read here)
         const int past = (int)((uint32_t)n / dom0.dom.B);  // first block that holds a rank >= n
         for (int t = threadIdx.x; t < blk_words; t += SHUF_TAB_THREADS)
-            s_lds[t] = t >= past ? ((uint32_t)(K - 1) | (0xFFFFu << 16)) : cum[kpad + t];
+            s_lds[t] = carry_entry(t >= past ? ((uint32_t)(K - 1) | (0xFFFFu << 16)) : cum[kpad + t]);
     } else {
         for (int t = threadIdx.x; t < kpad; t += SHUF_TAB_THREADS) s_cum[t] = cum[t];
         for (int t = threadIdx.x; t < blk_words; t += SHUF_TAB_THREADS) s_lds[t] = cum[kpad + t];
@@ -395,7 +408,7 @@ __global__ __launch_bounds__(SHUF_TAB_THREADS, 8) void k_shuffle_tab(int64_t n, 
     // the high digit is carried scaled by 4, the byte offset into the block table:  ((gsa + (x >> ash)) & am) << 2  ==
     // ((gsa << 2) + (x >> (ash - 2))) & (am << 2)  in every 16-bit half — the two low bits of x >> (ash - 2) never carry into a sum
     // that is masked above them, and ash >= 6 (A <= 1024) keeps a << 2 < 2^12 (tests/test_shuffle_valu_cpu.py)
-    const u16x2 am4 = (u16x2)((unsigned short)((dom.A - 1u) << 2));
+    const uint32_t am4w = (dom.A - 1u) << 2;  // the mask of ONE half: 4 (A - 1) < 2^12
     const u16x2 ash4 = (u16x2)((unsigned short)(dom.ash - 2u));
     uint32_t c1w = FEISTEL_C1 * 0x10001u;
     asm volatile("" : "+v"(c1w));  // opaque: stays a VGPR (shuf_tab_F2)
@@ -462,10 +475,16 @@ __global__ __launch_bounds__(SHUF_TAB_THREADS, 8) void k_shuffle_tab(int64_t n, 
                 const u16x2 k1 = __builtin_bit_cast(u16x2, ks[(w * 2 + jj) * 2 + 1]);
                 bpk[jj] = __builtin_bit_cast(uint32_t, b);
                 // gsa4 < 4A, x >> ash4 < 4A: < 8A <= 2^13 (A <= SHUF_TAB_MAX_A)
-                a4pk[jj] = __builtin_bit_cast(uint32_t, (u16x2)(add_nocarry(gsa4, shuf_tab_F2(b, k1, ash4, c1)) & am4));
-                const uint32_t e0 = blk_at(a4pk[jj] & 0xFFFFu);
-                const uint32_t e1 = blk_at(a4pk[jj] >> 16);
-                if (jj == 0) {
+                // the sum is kept unmasked: each half is masked where it becomes an address (the high one in one instruction, half
+                // select and mask) or, on the exact route, a digit
+                a4pk[jj] = __builtin_bit_cast(uint32_t, add_nocarry(gsa4, shuf_tab_F2(b, k1, ash4, c1)));
+                const uint32_t e0 = blk_at(a4pk[jj] & am4w);
+                const uint32_t e1 = blk_at((a4pk[jj] >> 16) & am4w);
+                if constexpr (FIX) {  // carry-form entries: the label is byte 2 of entry + b (carry_entry)
+                    const uint32_t r0 = e0 + (bpk[jj] & 0xFFFFu), r1 = e1 + (bpk[jj] >> 16);
+                    if (jj == 0) word = __builtin_amdgcn_perm(r1, r0, 0x0c0c0602u);  // bytes 0, 1; zeros above
+                    else word |= __builtin_amdgcn_perm(r1, r0, 0x06020c0cu);         // bytes 2, 3; zeros below
+                } else if (jj == 0) {
                     word = first_label(e0, bpk[jj], zero);
                     put_label<1, 1>(word, e1, bpk[jj], zero);
                 } else {
@@ -488,7 +507,7 @@ __global__ __launch_bounds__(SHUF_TAB_THREADS, 8) void k_shuffle_tab(int64_t n, 
                     if (K <= 255 && ((word >> (8 * j)) & 0xFFu) < (uint32_t)K) continue;
                     const int jj = j >> 1, sh = (j & 1) * 16;
                     const uint32_t* sk = ks + (w * 2 + jj) * 2;
-                    uint32_t a = ((a4pk[jj] >> sh) & 0xFFFFu) >> 2, b = (bpk[jj] >> sh) & 0xFFFFu;
+                    uint32_t a = ((a4pk[jj] >> sh) & am4w) >> 2, b = (bpk[jj] >> sh) & 0xFFFFu;
                     uint32_t x = a * dom.B + b;
                     if (x >= dom.n) {
                         const uint32_t k0 = (sk[0] >> sh) & 0xFFFFu, k1 = (sk[1] >> sh) & 0xFFFFu;
@@ -509,6 +528,12 @@ __global__ __launch_bounds__(SHUF_TAB_THREADS, 8) void k_shuffle_tab(int64_t n, 
                     word = (word & ~(0xFFu << (8 * j))) | (l << (8 * j));
                 }
             }
+            // The word is complete here, and the empty statement keeps it so: without the hand-written label instructions nothing
+            // orders the words, and the compiler sinks group A's sixteen look-ups below group B's arithmetic — 55 VGPRs instead of
+            // 39, 28 more wait states and a slower kernel, measured (profiles/shuffle_carry_before_after.md).  It is an asm
+            // statement without an instruction: a scheduling anchor whose worth rests on this compiler's scheduler — after a
+            // toolchain change read the instance's register count and measure the bracket with and without it again
+            if constexpr (FIX) asm volatile("" : "+v"(word));
             out[w] = word;
         }
     };
